@@ -12,6 +12,16 @@ collective; an all-reduce (RCCL) of the per-rank elapsed time (MAX) and byte cou
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size-gib 64] [--avg 4194304]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
+A plain run does what the headline needs and no more: it generates the stream, runs W
+warm-up and K timed passes, checks the last timed cut list against the oracle's golden
+record (the metric's "boundaries bit-exact": one hash of the list), writes it out when
+``--dump-outputs DIR`` is given (DIR/cuts.npy; cuts_rank<r>.npy per rank of a multi-GPU
+job) and prints the result line.  ``--full`` adds everything else after the timed
+region, each as a further key of the same line: the host-inclusive pass, the SURVEY 8(f)
+stages, the secondary random-data line and the CPU baselines; the options that select or
+size those (--stages, --digest, --blobs, --pipeline-gib, --upload-gib, --cpu-baseline,
+--cpu-config1, --host-inclusive-gib, --secondary-random) act under ``--full`` only.
+
 ``--gpus N`` without a launcher (no WORLD_SIZE in the environment) starts N rank
 processes itself (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set per child, 127.0.0.1) before
 anything touches the GPU, and fails (exit 2) when fewer than N devices are visible or
@@ -48,6 +58,14 @@ def parse():
     ap.add_argument("--mode", choices=["streams", "sharded"], default="streams",
                     help="streams: one independent stream per GPU (config 4); "
                          "sharded: one stream split over the GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the host-inclusive pass, the SURVEY 8(f) stages, "
+                         "the secondary random-data line and the CPU baselines (the options below that "
+                         "select or size them act only with this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's cut list (chunk END offsets, "
+                         "the stream end included) as DIR/cuts.npy, float64 (cuts_rank<r>.npy per rank of "
+                         "a multi-GPU job); a list beyond the size cap is a fixed seeded sample of itself")
     ap.add_argument("--cpu-baseline", type=int, default=1, help="0 to skip the CPU oracle timing")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline (0 = nproc: every CPU this process may run on)")
@@ -101,7 +119,36 @@ def parse():
                     help="the same for the secondary random-data line")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="PMC-derived HBM bytes per scan launch (written by profiles/collect_traffic.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        asked = [o for o, on in (("--digest", args.digest), ("--blobs", args.blobs), ("--stages", args.stages > 0),
+                                 ("--pipeline-gib", args.pipeline_gib > 0), ("--upload-gib", args.upload_gib > 0))
+                 if on]
+        if asked:
+            ap.error(f"{', '.join(asked)}: measured under --full only")
+        # a plain run: the headline and nothing after it
+        args.cpu_baseline = args.cpu_config1 = args.secondary_random = args.stages = 0
+        args.host_inclusive_gib = 0.0
+    return args
+
+
+DUMP_CAP = 64 * 1000 * 1000  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path_dir: str, cuts, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the
+    cut list (chunk END offsets, the stream end included) -- as float64 (offsets are below
+    2^53: exact).  One file per rank; all ranks together stay under DUMP_CAP: a longer list
+    is written as a fixed sample of itself (seed 0, positions ascending), the same in every
+    run of the same arguments."""
+    import numpy as np
+
+    c = np.asarray(cuts, dtype=np.uint64).astype(np.float64)
+    keep = (DUMP_CAP // max(1, world) - 4096) // 8  # (4096: room for the .npy header)
+    if c.size > keep:
+        c = c[np.sort(np.random.default_rng(0).choice(c.size, size=keep, replace=False))]
+    os.makedirs(path_dir, exist_ok=True)
+    np.save(os.path.join(path_dir, "cuts.npy" if world == 1 else f"cuts_rank{rank}.npy"), c)
 
 
 def stream_seed(workload: str, rank: int) -> int:
@@ -1113,6 +1160,8 @@ def standin_main(args, world: int, rank: int):
         c = oracle.chunk_feed(args.avg, buf)
         return np.append(c, np.uint64(size)) if size and (c.size == 0 or int(c[-1]) != size) else c
     elapsed, cuts = timed_steps(step, args, dist, lambda: None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cuts, rank, world)
     import socket
     rec = {"rank": rank, "seed": seed, "elapsed_s": elapsed, "bytes": size, "world_size": world,
            "device": {"kind": "cpu-standin", "host": socket.gethostname(), "pid": os.getpid()},
@@ -1229,6 +1278,8 @@ def main():
         last.update(t, ncuts=int(cuts.size))
 
     elapsed, cuts = timed_steps(step, args, dist, torch.cuda.synchronize, after)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cuts, rank, world)
     # after the timed region: this rank's last timed cut list against the oracle's golden
     # record of the same stream (tests/golden/bench_cuts.json)
     rec = {"rank": rank, "seed": seed, "elapsed_s": round(elapsed, 6), "bytes": work_bytes,

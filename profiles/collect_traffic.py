@@ -7,9 +7,9 @@ bench.py reports the traffic only for the same build.
 FETCH_SIZE is in KiB; on gfx950 it reports exactly half the bytes of a wide coalesced
 streaming read (MI355X_MICROARCH.md "HBM"), so bytes = FETCH_SIZE * 1024 * 2.
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run -- \
-        python bench.py --steps 3 --warmup 1 --cpu-baseline 0 --host-inclusive-gib 0
-    python profiles/collect_traffic.py gpurun_out/pmc_fetch --size-gib 64 --avg 4194304 --workload vmimage
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d profiles/out/pmc_fetch -o run -- \
+        python bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --host-inclusive-gib 0
+    python profiles/collect_traffic.py profiles/out/pmc_fetch --size-gib 64 --avg 4194304 --workload vmimage
 """
 import argparse
 import csv

@@ -13,7 +13,7 @@ step pmc 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$R/$O/pmc_fetch"
 python profiles/collect_traffic.py "$O/pmc_fetch" --out "$O/traffic.json" > "$O/collect.log" 2>&1 && cp "$O/traffic.json" profiles/traffic_latest.json
 step pmc_random 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$R/$O/pmc_fetch_random" -o run -- python bench.py --workload random --steps 3 --warmup 1 $NOEXTRA || exit 1
 python profiles/collect_traffic.py "$O/pmc_fetch_random" --workload random --out "$O/traffic_random.json" > "$O/collect_random.log" 2>&1 && cp "$O/traffic_random.json" profiles/traffic_random.json
-step bench_traced 400 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d "$R/$O/prof" -o run -- python bench.py || exit 1
+step bench_traced 400 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d "$R/$O/prof" -o run -- python bench.py --full || exit 1
 python scripts/frac_from_trace.py "$O/prof" --bench "$O/bench_traced.log" > "$O/frac_from_trace.json" 2>&1
-step bench 400 python bench.py || exit 1
+step bench 400 python bench.py --full || exit 1
 echo done

@@ -11,7 +11,7 @@ for p in 16384 65536 262144 1048576; do step ex_$p 120 examples/test_chunk_speed
 step zstd_corpus 300 python3 scripts/zstd_bench.py --corpus text,pxar,vm --gib 1 --reps 2 || exit 1
 step zstd_trace 300 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d "$R/$O/zstd_prof" -o run -- python3 scripts/zstd_bench.py --corpus text,pxar --gib 1 --reps 2 || exit 1
 python3 scripts/ktrace.py "$(ls $O/zstd_prof/*.db $O/zstd_prof/*/*.db 2>/dev/null | head -1)" zstd > "$O/zstd_ktrace.txt" 2>&1
-step upload_pxar 300 python bench.py --steps 2 --warmup 1 $NOEXTRA --upload-gib 16 --upload-corpus pxar || exit 1
+step upload_pxar 300 python bench.py --steps 2 --warmup 1 --full $NOEXTRA --upload-gib 16 --upload-corpus pxar || exit 1
 step c2 200 python bench.py --steps 50 --warmup 30 $NOEXTRA --size-gib 8 --workload random || exit 1
 step c5 200 python bench.py --steps 10 --warmup 3 $NOEXTRA --avg 262144 || exit 1
 echo done

@@ -186,6 +186,56 @@ def test_bench_verification_fails_loudly(tmp_path):
     assert rc == 0 and "verified" not in out
 
 
+def test_bench_dump_outputs_standin(oracle, tmp_path):
+    """--dump-outputs writes every rank's last timed cut list as float64 .npy (one file per
+    rank of a 2-rank job), equal to the oracle's list and the same from run to run."""
+    import numpy as np
+    size = int(0.01 * (1 << 30)) // 8 * 8
+    got = []
+    for d in ("a", "b"):
+        rc, out, err = _run_bench(["--gpus", "2", "--cpu-standin", "--size-gib", "0.01", "--avg", "65536",
+                                   "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / d)])
+        assert rc == 0, err[-2000:]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["cuts_rank0.npy", "cuts_rank1.npy"]
+        got.append([np.load(tmp_path / d / f"cuts_rank{r}.npy") for r in range(2)])
+    for r, rec in enumerate(sorted(out["per_rank"], key=lambda x: x["rank"])):
+        a = got[0][r]
+        assert a.dtype == np.float64 and np.array_equal(a, got[1][r])
+        assert [int(x) for x in a] == _oracle_cuts(oracle, "vmimage", rec["seed"], size, 65536)
+
+
+def test_bench_extras_need_full():
+    """The measurements beyond the headline run under --full: asking for one without it
+    fails loudly (argparse, exit 2) instead of printing a line without it."""
+    for extra in (["--digest", "1"], ["--blobs", "1"], ["--stages", "1"], ["--pipeline-gib", "1"],
+                  ["--upload-gib", "1"]):
+        rc, out, err = _run_bench(["--gpus", "1", "--steps", "1"] + extra, timeout=120)
+        assert rc == 2 and out is None and "--full" in err, (extra, err[-500:])
+
+
+def test_bench_dump_sample_is_fixed(tmp_path):
+    """A cut list beyond the size cap is written as a seeded sample of itself: ascending,
+    within the cap, the same every time."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    cuts = np.arange(1, 1001, dtype=np.uint64) * 7
+    old = bench.DUMP_CAP
+    bench.DUMP_CAP = 2 * (4096 + 8 * 100)  # 100 values per rank of a 2-rank job
+    try:
+        bench.dump_outputs(str(tmp_path / "a"), cuts, 1, 2)
+        bench.dump_outputs(str(tmp_path / "b"), cuts, 1, 2)
+    finally:
+        bench.DUMP_CAP = old
+    a, b = np.load(tmp_path / "a" / "cuts_rank1.npy"), np.load(tmp_path / "b" / "cuts_rank1.npy")
+    assert a.dtype == np.float64 and a.size == 100 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.isin(a, cuts.astype(np.float64)).all()
+    assert os.path.getsize(tmp_path / "a" / "cuts_rank1.npy") <= 4096 + 8 * 100
+
+
 def test_bench_golden_script_pinned(oracle):
     """tests/golden/make_bench_golden.py reproduces its committed small entries, and its
     streaming oracle (ora_chunk_generated, the stream generated 16 MiB at a time) equals
@@ -279,3 +329,32 @@ def test_bench_rccl_world1(oracle, mode):
     assert r["bytes"] == size
     assert r["cuts"] == _oracle_cuts(oracle, "vmimage", r["seed"], size, 4 << 20)
     assert out["value"] == pytest.approx(size * 2 / (1 << 30) / r["elapsed_s"], rel=1e-2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_plain_and_full_lines(oracle, tmp_path, full):
+    """A plain run prints the headline alone (verified, with ms_per_step for exactly --steps
+    timed steps) and --dump-outputs writes the cut list its last step returned; --full adds
+    the measurements after the timed region to the same line, headline keys unchanged."""
+    import numpy as np
+    gib = 0.25
+    size = int(gib * (1 << 30)) // 8 * 8
+    # (no golden record of a 0.25 GiB random stream: the secondary line stays off)
+    extra = ["--full", "--cpu-config1", "0", "--cpu-sample-mib", "8", "--cpu-threads", "2",
+             "--secondary-random", "0"] if full else []
+    rc, out, err = _run_bench(["--gpus", "1", "--size-gib", str(gib), "--steps", "3", "--warmup", "1",
+                               "--dump-outputs", str(tmp_path)] + extra, timeout=240)
+    assert rc == 0, err[-2000:]
+    assert out["verified"] is True and out["steps"] == 3 and out["unit"] == "GiB/s" and out["dtype"] == "u8"
+    assert out["higher_is_better"] is True and "GiB/s chunked" in out["metric"]
+    (r,) = out["per_rank"]
+    assert out["ms_per_step"] == pytest.approx(r["elapsed_s"] / 3 * 1e3, rel=1e-2)
+    assert out["value"] == pytest.approx(size * 3 / (1 << 30) / r["elapsed_s"], rel=1e-2)
+    ref = _oracle_cuts(oracle, "vmimage", r["seed"], size, 4 << 20)
+    assert os.listdir(tmp_path) == ["cuts.npy"]
+    cuts = np.load(tmp_path / "cuts.npy")
+    assert cuts.dtype == np.float64 and [int(x) for x in cuts] == ref == r["cuts"]
+    more = {"cpu_baseline", "host_inclusive_gib_s"}
+    assert more <= set(out) if full else not (more & set(out))
+    assert "secondary_random" not in out

@@ -140,6 +140,7 @@ struct ScanServer {
     bool dev_req = true;   // PBS_SERVER_VRAM=0: record + slot in pinned host memory (A/B)
     hipStream_t stream = nullptr;
     uint64_t seq = 0;
+    uint64_t served = 0;  // requests whose candidates were taken (tests: pbs_test_handle_stats)
     bool running = false;
     bool enabled = true;  // PBS_SCAN_SERVER=0: every scan() takes the batch path (A/B)
     bool broken = false;  // a request timed out: never used again by this handle
@@ -879,6 +880,7 @@ int server_scan(pbs_chunker* c, const uint8_t* hsrc, uint64_t pos, uint64_t bl, 
     c->timing.candidates += k;
     update_carry(c, hsrc, bl);
     c->scanned_end = pos + bl;
+    ++sv.served;
     *served = true;
     return PBS_OK;
 }
@@ -2009,6 +2011,41 @@ int pbs_test_fused_static_plan(uint64_t len, uint64_t nw, uint64_t* out) {
     out[6] = ((a.t_small * a.seg_q + a.t_long) + (a.ntiles - a.t_small) * a.seg_qs + a.t_small_long) *
              64 * kBlockBytes;
     out[7] = a.pool;
+    return PBS_OK;
+}
+
+// Test hook: the tile plan of scan_main_kernel (and of the dynamic order of the fused pass)
+// for a batch of `len` bytes on `cu` compute units -- out = {seg, ntiles, t_big, dyn, covered
+// bytes}: tiles [0, t_big) have 64 segments of seg bytes, the rest of seg / 4.
+int pbs_test_scan_main_plan(uint64_t len, int cu, uint64_t* out) {
+    if (!out || cu < 1) return PBS_ERR_INVALID;
+    uint64_t ntiles = 0, t_big = 0;
+    bool dyn = false;
+    const int seg = scan_main_plan(len, cu, &ntiles, &dyn, &t_big);
+    out[0] = (uint64_t)seg;
+    out[1] = ntiles;
+    out[2] = t_big;
+    out[3] = dyn ? 1 : 0;
+    out[4] = scan_main_covered(ntiles, t_big, seg);
+    return PBS_OK;
+}
+
+// Test hook: the 16-bit tile-record epoch of the handle's last fused / scan pass (the next
+// pass uses v + 1; at 0xFFFF it wraps: the records are zeroed and the epoch restarts at 1).
+int pbs_test_set_fused_epoch(pbs_chunker* c, uint32_t v) {
+    if (!c || v > 0xFFFFu) return PBS_ERR_INVALID;
+    c->rec_epoch = v;
+    return PBS_OK;
+}
+
+// Test hook: out = {scan-server requests sent, requests served (the others overflowed and
+// went to the batch path), server given up (0/1), tile-record epoch of the last pass}.
+int pbs_test_handle_stats(const pbs_chunker* c, uint64_t* out) {
+    if (!c || !out) return PBS_ERR_INVALID;
+    out[0] = c->srv.seq;
+    out[1] = c->srv.served;
+    out[2] = c->srv.broken ? 1 : 0;
+    out[3] = c->rec_epoch;
     return PBS_OK;
 }
 

@@ -220,6 +220,11 @@ def lib():
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
+        # test hooks (not in include/): tile plans and the fused pass's record epoch
+        "pbs_test_fused_static_plan": ([u64, u64, ctypes.POINTER(u64)], i),
+        "pbs_test_scan_main_plan": ([u64, i, ctypes.POINTER(u64)], i),
+        "pbs_test_set_fused_epoch": ([p, ctypes.c_uint32], i),
+        "pbs_test_handle_stats": ([p, ctypes.POINTER(u64)], i),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("PBS_LIBPBSCHUNK_AB") and not hasattr(L, name):
@@ -394,6 +399,16 @@ class Chunker:
     def reset(self):
         self._check(lib().pbs_chunker_reset(self._h), "pbs_chunker_reset")
 
+    def stats_for_test(self) -> dict:
+        """Test hook: scan-server requests sent / served / given up, and the record epoch."""
+        out = (ctypes.c_uint64 * 4)()
+        self._check(lib().pbs_test_handle_stats(self._h, out), "pbs_test_handle_stats")
+        return dict(zip(("requests", "served", "broken", "epoch"), (int(x) for x in out)))
+
+    def set_fused_epoch_for_test(self, v: int):
+        """Test hook: the 16-bit tile-record epoch of the last fused / scan pass."""
+        self._check(lib().pbs_test_set_fused_epoch(self._h, int(v)), "pbs_test_set_fused_epoch")
+
     @property
     def stream_offset(self) -> int:
         return int(lib().pbs_chunker_stream_offset(self._h))
@@ -517,6 +532,25 @@ def candidates_host(data, avg: int) -> np.ndarray:
     if rc != PBS_OK:
         raise ChunkerError(rc, "pbs_candidates_host")
     return out[: n.value].copy()
+
+
+def plan_fused_static(length: int, nw: int) -> dict:
+    """Test hook: the static tile plan of the fused pass over ``nw`` scanner waves."""
+    out = (ctypes.c_uint64 * 8)()
+    rc = lib().pbs_test_fused_static_plan(int(length), int(nw), out)
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_test_fused_static_plan")
+    keys = ("ntiles", "seg_q", "t_long", "t_small", "seg_qs", "t_small_long", "covered", "pool")
+    return dict(zip(keys, (int(x) for x in out)))
+
+
+def plan_scan_main(length: int, cu: int) -> dict:
+    """Test hook: scan_main's tile plan (tiles [0, t_big) of 64 x seg bytes, then seg / 4)."""
+    out = (ctypes.c_uint64 * 5)()
+    rc = lib().pbs_test_scan_main_plan(int(length), int(cu), out)
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_test_scan_main_plan")
+    return dict(zip(("seg", "ntiles", "t_big", "dyn", "covered"), (int(x) for x in out)))
 
 
 def generate_device(dev_ptr: int, length: int, kind: int, seed: int, offset: int = 0,

@@ -52,7 +52,7 @@ size_t pbs_blob_encode_uncompressed(const uint8_t *data, size_t len, uint32_t cr
                                     size_t cap);
 
 /* DataBlob images of every chunk on the GPU (`DataBlob::encode(data, None, compress)`,
- * data_blob.rs:87-176, unencrypted path).  compress != 0: each chunk is compressed into a
+ * data_blob.rs:87-176, unencrypted path; the encrypted one is at the end of this file).  compress != 0: each chunk is compressed into a
  * zstd frame (64 KiB blocks: RLE, compressed -- Huffman, raw or RLE literals; sequences
  * with repeat offsets and predefined, RLE or own FSE tables -- or raw; the match window
  * reaches 16 KiB before each 8 KiB sub-block; decodable by any zstd decoder, the reference's
@@ -92,6 +92,63 @@ void pbs_blob_encode_release(void);
 size_t pbs_blob_stream_bound(const uint64_t *bounds, size_t n);
 /* Largest zstd frame this encoder writes for `len` bytes (header + raw blocks). */
 size_t pbs_zstd_frame_bound(size_t len);
+
+/* ---- Encrypted blobs: the `Some(config)` half of DataBlob::encode (data_blob.rs:107-131) ----
+ *
+ * Blob i is magic[8] || crc LE[4] || iv[16] || tag[16] || ciphertext
+ * (EncryptedDataBlobHeader, file_formats.rs:47-58): AES-256-GCM with a 16-byte IV and empty
+ * AAD under the config's key; the plaintext is the zstd frame (ENCR_COMPR_BLOB_MAGIC_1_0)
+ * when compress != 0 and the frame is shorter than the chunk (data_blob.rs:98-105), else the
+ * chunk bytes (ENCRYPTED_BLOB_MAGIC_1_0); the CRC covers the ciphertext only. */
+#define PBS_BLOB_ENC_HEADER_SIZE 44 /* EncryptedDataBlobHeader: magic[8] crc[4] iv[16] tag[16] */
+#define PBS_GCM_SEGMENT_BYTES 65536 /* payload bytes one workgroup encrypts and hashes */
+#define PBS_ERR_ARG PBS_ERR_INVALID /* bad argument (pbs_chunker.h's code, -6) */
+
+/* `CryptConfig::new(enc_key)` (pbs-tools/src/crypt_config.rs:42-61): derives
+ * id_key = PBKDF2-HMAC-SHA256(enc_key, "_id_key", 10 rounds, 32 bytes), the 15 AES-256 round
+ * keys, H = AES_K(0^128) and the per-key GHASH tables.  The handle keeps no copy of enc_key;
+ * pbs_crypt_config_free zeroes everything derived from it (host and device copies) before
+ * the memory is released.  No key byte appears in any error text.  A handle may be used by
+ * several threads and devices at once; free it when no call is using it. */
+typedef struct pbs_crypt_config pbs_crypt_config;
+int pbs_crypt_config_new(const uint8_t enc_key[32], pbs_crypt_config **out);
+/* The 32-byte id_key (`CryptConfig::compute_digest` appends it to every chunk: pass it as
+ * the digest `key` of pbs_digest.h).  Valid until the handle is freed. */
+const uint8_t *pbs_crypt_config_id_key(const pbs_crypt_config *cfg);
+void pbs_crypt_config_free(pbs_crypt_config *cfg);
+
+/* AES-256-GCM of one buffer on the host with the same AES / GF(2^128) code the kernels use
+ * (`Crypter::new(aes_256_gcm, Encrypt, key, Some(iv16))`, empty AAD): `out` (len bytes, may
+ * alias `data`) and the 16-byte `tag`.  For tests and small blobs; not a fast path. */
+int pbs_aes256gcm_encrypt_host(const pbs_crypt_config *cfg, const uint8_t iv[16], const uint8_t *data,
+                               size_t len, uint8_t *out, uint8_t tag[16]);
+
+/* pbs_blob_encode_{spans,chunks}_device with encryption.  `ivs`: NULL (the product mode: the
+ * library draws 16 fresh bytes per blob from getrandom(2), as data_blob.rs:113 does) or 16 n
+ * host bytes, IV i for blob i -- for reproducible tests only: REUSING AN IV UNDER ONE KEY
+ * BREAKS GCM (it reveals the XOR of the plaintexts and lets tags be forged).
+ * `cfg` NULL: PBS_ERR_ARG.  blobs_cap below pbs_blob_stream_bound_encrypted (44 n + the
+ * chunks' bytes): PBS_ERR_CAPACITY before anything is written.  `timing->base` as in the
+ * unencrypted call (crc_ms: the ciphertext CRCs + headers). */
+typedef struct {
+    pbs_blob_encode_timing base;
+    double encrypt_ms;     /* IV/J0 setup, CTR + GHASH in place, tags (HIP events) */
+    uint64_t gcm_segments; /* PBS_GCM_SEGMENT_BYTES pieces encrypted */
+} pbs_blob_encode_timing_crypt;
+int pbs_blob_encode_chunks_encrypted_device(const uint8_t *dev_data, size_t data_len, uint64_t base,
+                                            const uint64_t *bounds, size_t n, int compress,
+                                            const pbs_crypt_config *cfg, const uint8_t *ivs,
+                                            uint8_t *blobs_dev, size_t blobs_cap, uint64_t *blob_offsets,
+                                            uint32_t *crcs, uint8_t *compressed,
+                                            pbs_blob_encode_timing_crypt *timing, void *hip_stream);
+int pbs_blob_encode_spans_encrypted_device(const uint8_t *dev_data, size_t data_len, uint64_t base,
+                                           const uint64_t *spans, size_t n, int compress,
+                                           const pbs_crypt_config *cfg, const uint8_t *ivs,
+                                           uint8_t *blobs_dev, size_t blobs_cap, uint64_t *blob_offsets,
+                                           uint32_t *crcs, uint8_t *compressed,
+                                           pbs_blob_encode_timing_crypt *timing, void *hip_stream);
+/* 44 n + (bounds[n] - bounds[0]): the largest encrypted blob stream of n chunks. */
+size_t pbs_blob_stream_bound_encrypted(const uint64_t *bounds, size_t n);
 
 #ifdef __cplusplus
 }

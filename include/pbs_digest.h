@@ -179,6 +179,22 @@ int pbs_upload_stream_host(size_t avg, const uint8_t *host, size_t len, size_t p
                            size_t blobs_cap, uint64_t *blob_offsets, uint8_t *compressed,
                            pbs_upload_timing *timing);
 
+/* pbs_upload_stream_host for an encrypted backup (`crypt`: pbs_crypt_config_new of
+ * include/pbs_blob.h; NULL: PBS_ERR_INVALID).  The digests are SHA-256(chunk || id_key) with
+ * the config's id_key (backup_writer.rs:671-678, DataChunkBuilder::crypt_config), the
+ * known-chunk test is unchanged, and every new chunk becomes an encrypted blob
+ * (pbs_blob_encode_spans_encrypted_device with library-drawn IVs: 44-byte headers, so
+ * `blobs_cap` >= 44 n + len covers any stream).  size_compressed counts the encrypted
+ * blobs' raw sizes.  `encrypt_ms` (may be NULL): the GPU time of the AES-GCM launches,
+ * summed over the pieces. */
+struct pbs_crypt_config;
+int pbs_upload_stream_host_crypt(size_t avg, const uint8_t *host, size_t len, size_t piece,
+                                 const struct pbs_crypt_config *crypt, int digest_cus,
+                                 const uint8_t *known, size_t n_known, int compress, uint64_t *ends,
+                                 uint8_t *digests, uint8_t *is_known, size_t cap, size_t *n_out,
+                                 uint8_t *blobs, size_t blobs_cap, uint64_t *blob_offsets,
+                                 uint8_t *compressed, pbs_upload_timing *timing, double *encrypt_ms);
+
 /* Frees the idle pipeline work areas (device memory of the last stream lengths). */
 void pbs_pipeline_release(void);
 

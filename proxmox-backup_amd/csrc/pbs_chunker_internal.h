@@ -3,7 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef struct pbs_chunker pbs_chunker;  // include/pbs_chunker.h
+#include <vector>
+
+typedef struct pbs_chunker pbs_chunker;            // include/pbs_chunker.h
+typedef struct pbs_crypt_config pbs_crypt_config;  // include/pbs_blob.h
 
 namespace pbs {
 
@@ -141,6 +144,19 @@ hipError_t exclusive_sum_u64(void* tmp, size_t* tmp_bytes, const uint64_t* in, u
 // pbs_blob.hip: CRC-32 of blob payloads [bounds[i] + skip, bounds[i+1]) of `data`
 hipError_t launch_crc32_skip(const uint8_t* data, const uint64_t* bounds_dev, uint64_t n, uint64_t skip,
                              uint32_t* out, hipStream_t st);
+// pbs_crypt.hip: AES-256-GCM in place over the payloads of n blob images (plaintext at
+// blob + 44; blob i = [boff[i], boff[i+1]), offsets on host and device), IV and tag into the
+// headers; asynchronous on `st`.  Takes 5 arena slots from `slot0`; `hs` holds the host
+// arrays of the copies and must outlive the stream's next synchronisation.
+struct GcmHostScratch {
+    std::vector<uint8_t> ivs;
+    std::vector<uint64_t> items, first;
+    uint64_t segments = 0;
+};
+class DevArena;
+int gcm_encrypt_blobs(const pbs_crypt_config* cfg, uint8_t* blobs, const uint64_t* boff_host,
+                      const uint64_t* boff_dev, size_t n, const uint8_t* ivs_host, DevArena& ar, unsigned slot0,
+                      GcmHostScratch& hs, hipStream_t st);
 hipError_t inclusive_max_u32(void* tmp, size_t* tmp_bytes, const uint32_t* in, uint32_t* out,
                              uint64_t n, hipStream_t stream);
 // m_dev != nullptr: the node count is m_base + *m_dev, on the device only; m is then its upper

@@ -198,7 +198,25 @@ struct UploadExt {
     double known_ms = 0, enc_ms = 0, d2h_ms = 0;
     pbs_blob_encode_timing enc_t{};
     int enc_rc = PBS_OK;
+    // pbs_upload_stream_host_crypt: the new chunks become encrypted blobs (44-byte headers)
+    const pbs_crypt_config* crypt = nullptr;
+    double encrypt_ms = 0;
 };
+
+// DataBlob::encode of `cnt` spans with the upload's crypt config, if any
+int encode_upload_spans(const UploadExt& x, const uint8_t* d_data, size_t len, const uint64_t* sp, size_t cnt,
+                        uint8_t* d_blobs, size_t cap, uint64_t* offs, uint8_t* comp, pbs_blob_encode_timing* bt,
+                        double* encrypt_ms, hipStream_t st) {
+    if (!x.crypt)
+        return pbs_blob_encode_spans_device(d_data, len, 0, sp, cnt, x.compress, d_blobs, cap, offs, nullptr, comp, bt,
+                                            st);
+    pbs_blob_encode_timing_crypt ct{};
+    const int r = pbs_blob_encode_spans_encrypted_device(d_data, len, 0, sp, cnt, x.compress, x.crypt, nullptr,
+                                                         d_blobs, cap, offs, nullptr, comp, &ct, st);
+    if (bt) *bt = ct.base;
+    if (encrypt_ms) *encrypt_ms += ct.encrypt_ms;
+    return r;
+}
 
 int upload_stage(UploadExt& x, pbs::DevArena* area, const uint8_t* d_data, size_t len, const uint64_t* ends,
                  const uint8_t* digests, size_t n, hipStream_t st);
@@ -439,7 +457,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     if (ok && ext && env_u64("PBS_UPLOAD_SPEC", 1) != 0) {
         // every chunk's blob (the early encode writes the whole batch: <= len + 12 per chunk)
         // plus up to 15 bytes of alignment per batch (a batch holds >= 1 chunk): 27 per chunk
-        const size_t bcap = len + 28 * cap + 64;
+        const size_t bcap = len + (ext->crypt ? 60 : 28) * cap + 64;
         ext->d_blobs = area->get<uint8_t>(9, bcap, false);
         if (ext->d_blobs) {
             ext->spec = true;
@@ -495,9 +513,9 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
                         pbs_blob_encode_timing bt{};
                         int r = hipStreamWaitEvent(su, ev_copied[b[2]], 0) == hipSuccess ? PBS_OK : PBS_ERR_HIP;
                         if (r == PBS_OK)
-                            r = pbs_blob_encode_spans_device(d_data, len, 0, sp.data(), cnt, ext->compress,
-                                                             ext->d_blobs + dbase, bcap - dbase, offm.data(), nullptr,
-                                                             compm.data(), &bt, su);
+                            r = encode_upload_spans(*ext, d_data, len, sp.data(), cnt, ext->d_blobs + dbase,
+                                                    bcap - dbase, offm.data(), compm.data(), &bt,
+                                                    &ext->encrypt_ms, su);
                         ext->enc_ms += ms_since(te);
                         ext->enc_t.compress_ms += bt.compress_ms;
                         ext->enc_t.assemble_ms += bt.assemble_ms;
@@ -909,13 +927,13 @@ int upload_stage(UploadExt& x, pbs::DevArena* area, const uint8_t* d_data, size_
         new_bytes += b - a;
     }
     const size_t m = idx.size();
-    const size_t bound = 12 * m + new_bytes;
+    const size_t bound = (x.crypt ? PBS_BLOB_ENC_HEADER_SIZE : PBS_BLOB_HEADER_SIZE) * m + new_bytes;
     uint8_t* const d_blobs = area->get<uint8_t>(9, std::max<size_t>(bound, 1), false);
     if (!d_blobs) return PBS_ERR_NOMEM;
     std::vector<uint64_t> offm(m + 1, 0);
     std::vector<uint8_t> compm(std::max<size_t>(m, 1), 0);
-    rc = pbs_blob_encode_spans_device(d_data, len, 0, spans.data(), m, x.compress, d_blobs, bound, offm.data(),
-                                      nullptr, compm.data(), t ? &t->blob : nullptr, st);
+    rc = encode_upload_spans(x, d_data, len, spans.data(), m, d_blobs, bound, offm.data(), compm.data(),
+                             t ? &t->blob : nullptr, &x.encrypt_ms, st);
     if (rc != PBS_OK) return rc;
     const Clock::time_point t2 = Clock::now();
     if (offm[m] > x.blobs_cap) return PBS_ERR_CAPACITY;
@@ -971,5 +989,27 @@ extern "C" int pbs_upload_stream_host(size_t avg, const uint8_t* host, size_t le
     const int rc = pipeline_run(avg, host, len, piece, key, key_len, digest_cus, ends, digests, nullptr, cap, n_out,
                                 timing ? &timing->pipe : nullptr, len ? &x : nullptr);
     if (timing) timing->total_ms = ms_since(t0);
+    return rc;
+}
+
+extern "C" int pbs_upload_stream_host_crypt(size_t avg, const uint8_t* host, size_t len, size_t piece,
+                                            const pbs_crypt_config* crypt, int digest_cus, const uint8_t* known,
+                                            size_t n_known, int compress, uint64_t* ends, uint8_t* digests,
+                                            uint8_t* is_known, size_t cap, size_t* n_out, uint8_t* blobs,
+                                            size_t blobs_cap, uint64_t* blob_offsets, uint8_t* compressed,
+                                            pbs_upload_timing* timing, double* encrypt_ms) {
+    if (!crypt) return PBS_ERR_ARG;
+    if (!is_known || !blob_offsets || (n_known && !known) || (blobs_cap && !blobs)) return PBS_ERR_INVALID;
+    if (timing) std::memset(timing, 0, sizeof(*timing));
+    if (encrypt_ms) *encrypt_ms = 0;
+    blob_offsets[0] = 0;
+    const Clock::time_point t0 = Clock::now();
+    UploadExt x{known, n_known, compress, is_known, blobs, blobs_cap, blob_offsets, compressed, timing};
+    x.crypt = crypt;
+    // DataChunkBuilder::crypt_config: the digests are SHA-256(chunk || id_key)
+    const int rc = pipeline_run(avg, host, len, piece, pbs_crypt_config_id_key(crypt), 32, digest_cus, ends, digests,
+                                nullptr, cap, n_out, timing ? &timing->pipe : nullptr, len ? &x : nullptr);
+    if (timing) timing->total_ms = ms_since(t0);
+    if (encrypt_ms) *encrypt_ms = x.encrypt_ms;
     return rc;
 }

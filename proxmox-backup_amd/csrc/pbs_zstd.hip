@@ -114,6 +114,9 @@ static_assert(kZTab * 2 * kZWaves == 64 * 1024, "the tables fill the work area")
 // pbs-datastore/src/file_formats.rs:9, :12
 constexpr uint8_t kUncompressedMagic[8] = {66, 171, 56, 7, 190, 131, 112, 161};
 constexpr uint8_t kCompressedMagic[8] = {49, 185, 88, 66, 111, 182, 163, 127};
+// ENCRYPTED_BLOB_MAGIC_1_0 / ENCR_COMPR_BLOB_MAGIC_1_0, pbs-datastore/src/file_formats.rs:15,18
+constexpr uint8_t kEncryptedMagic[8] = {123, 103, 133, 190, 34, 45, 76, 240};
+constexpr uint8_t kEncrComprMagic[8] = {230, 89, 27, 191, 11, 191, 216, 11};
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
@@ -3420,7 +3423,7 @@ __global__ __launch_bounds__(kEThreads) __attribute__((amdgpu_waves_per_eu(3, 3)
 // Per chunk: frame size, compressed-or-not, blob size.  fsz[n] = 0 (scan padding).
 __global__ void zstd_frame_sizes_kernel(const uint64_t* __restrict__ bounds, const uint64_t* __restrict__ first,
                                         const uint64_t* __restrict__ sizes, uint64_t n, int compress,
-                                        uint64_t* __restrict__ bsz, uint8_t* __restrict__ comp) {
+                                        uint64_t* __restrict__ bsz, uint8_t* __restrict__ comp, uint32_t hdr) {
     const uint64_t ci = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ci > n) return;
     if (ci == n) {
@@ -3436,7 +3439,7 @@ __global__ void zstd_frame_sizes_kernel(const uint64_t* __restrict__ bounds, con
         c = fs < len;  // data_blob.rs:153: only if shorter
     }
     comp[ci] = c ? 1 : 0;
-    bsz[ci] = 12 + (c ? fs : len);
+    bsz[ci] = hdr + (c ? fs : len);
 }
 
 // Per item: its part of the blob image.  Compressed chunk: the block (and, for the first
@@ -3445,7 +3448,8 @@ __global__ __launch_bounds__(kZThreads) void zstd_assemble_kernel(
     const uint8_t* __restrict__ data, uint64_t base, const uint64_t* __restrict__ bounds,
     const uint64_t* __restrict__ items, uint64_t nitems, const uint64_t* __restrict__ first,
     const uint8_t* __restrict__ slots, const uint64_t* __restrict__ sizes, const uint64_t* __restrict__ ipre,
-    const uint64_t* __restrict__ boff, const uint8_t* __restrict__ comp, uint8_t* __restrict__ blobs) {
+    const uint64_t* __restrict__ boff, const uint8_t* __restrict__ comp, uint8_t* __restrict__ blobs,
+    uint32_t hdr) {  // hdr: 12, or 44 for a blob that will be encrypted in place (pbs_crypt.hip)
     for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
         const uint64_t it = items[k];
         const uint64_t ci = it >> 32, j = (uint32_t)it;
@@ -3453,16 +3457,19 @@ __global__ __launch_bounds__(kZThreads) void zstd_assemble_kernel(
         uint8_t* const blob = blobs + boff[ci];
         const bool c = comp[ci] != 0;
         const uint32_t fh = frame_header_size(len);
-        if (j == 0 && threadIdx.x < 8) blob[threadIdx.x] = c ? kCompressedMagic[threadIdx.x] : kUncompressedMagic[threadIdx.x];
+        if (j == 0 && threadIdx.x < 8)
+            blob[threadIdx.x] = hdr == PBS_BLOB_HEADER_SIZE
+                                    ? (c ? kCompressedMagic[threadIdx.x] : kUncompressedMagic[threadIdx.x])
+                                    : (c ? kEncrComprMagic[threadIdx.x] : kEncryptedMagic[threadIdx.x]);
         if (c) {
-            if (j == 0 && threadIdx.x == 0) write_frame_header(blob + 12, len);
-            uint8_t* const dst = blob + 12 + fh + (ipre[k] - ipre[first[ci]]);
+            if (j == 0 && threadIdx.x == 0) write_frame_header(blob + hdr, len);
+            uint8_t* const dst = blob + hdr + fh + (ipre[k] - ipre[first[ci]]);
             copy_global(dst, slots + k * kSlot, sizes[k], threadIdx.x, kZThreads);
         } else {
             const uint64_t off = j * (uint64_t)kEncBlock;
             const uint64_t n = len > off ? (len - off < kEncBlock ? len - off : kEncBlock) : 0;
             const uint8_t* const src = data + (bounds[2 * ci] - base) + off;
-            copy_global(blob + 12 + off, src, n, threadIdx.x, kZThreads);
+            copy_global(blob + hdr + off, src, n, threadIdx.x, kZThreads);
         }
     }
 }
@@ -3488,7 +3495,8 @@ ArenaPool& zpool() {
     return *p;
 }
 enum ZSlot : unsigned { kZsBounds, kZsItems, kZsFirst, kZsSizes, kZsIpre, kZsBsz, kZsBoff, kZsComp, kZsCrc, kZsTmp,
-                        kZsSlots, kZsSeqs, kZsCoded, kZsChains, kZsZItems, kZsLits, kZsDeal, kZsEList };
+                        kZsSlots, kZsSeqs, kZsCoded, kZsChains, kZsZItems, kZsLits, kZsDeal, kZsEList,
+                        kZsGcm /* 5 slots of pbs_crypt.hip */ };
 
 }  // namespace
 }  // namespace pbs
@@ -3510,14 +3518,16 @@ extern "C" size_t pbs_blob_stream_bound(const uint64_t* bounds, size_t n) {
 }
 
 // The chunks as spans {start, end} (absolute stream offsets; any order, gaps allowed):
-// pbs_blob_encode_spans_device, and pbs_blob_encode_chunks_device through it.
-extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data_len, uint64_t base,
-                                            const uint64_t* spans, size_t n, int compress, uint8_t* blobs_dev,
-                                            size_t blobs_cap, uint64_t* blob_offsets, uint32_t* crcs,
-                                            uint8_t* compressed, pbs_blob_encode_timing* timing,
-                                            void* hip_stream) {
+// pbs_blob_encode_spans_device, and pbs_blob_encode_chunks_device through it.  `cfg`: NULL,
+// or the crypt config of the encrypted entry points -- the images are then assembled with
+// the 44-byte header and encrypted in place before the CRC; `ct` receives that step's time.
+static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base, const uint64_t* spans, size_t n,
+                        int compress, const pbs_crypt_config* cfg, const uint8_t* ivs, uint8_t* blobs_dev,
+                        size_t blobs_cap, uint64_t* blob_offsets, uint32_t* crcs, uint8_t* compressed,
+                        pbs_blob_encode_timing* timing, pbs_blob_encode_timing_crypt* ct, void* hip_stream) {
     using Clock = std::chrono::steady_clock;
     const Clock::time_point t0 = Clock::now();
+    const uint32_t hdr = cfg ? PBS_BLOB_ENC_HEADER_SIZE : PBS_BLOB_HEADER_SIZE;
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (!blob_offsets) return PBS_ERR_INVALID;
     blob_offsets[0] = 0;
@@ -3531,6 +3541,8 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
         if (spans[2 * i + 1] - spans[2 * i] > (128ull << 20)) return PBS_ERR_INVALID;
         bytes_in += spans[2 * i + 1] - spans[2 * i];
     }
+    // encrypted: the full bound up front, so a short buffer is refused before any launch
+    if (cfg && blobs_cap < (uint64_t)PBS_BLOB_ENC_HEADER_SIZE * n + bytes_in) return PBS_ERR_CAPACITY;
     const uint64_t* const bounds = spans;  // (device copies below: 2 n entries)
     hipStream_t st = (hipStream_t)hip_stream;
     int dev = 0, ncu = 0;
@@ -3640,8 +3652,9 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
     }
     if (!d_bounds || !d_items || !d_first || !d_sizes || !d_ipre || !d_bsz || !d_boff || !d_comp || !d_crc || !d_tmp)
         fail(PBS_ERR_NOMEM);
-    hipEvent_t ev[4] = {};
-    for (unsigned i = 0; i < 4 && rc == PBS_OK; ++i)
+    hipEvent_t ev[5] = {};
+    GcmHostScratch gcm_host;
+    for (unsigned i = 0; i < (cfg ? 5u : 4u) && rc == PBS_OK; ++i)
         if (!(ev[i] = ar->event(i))) fail(PBS_ERR_HIP);
     if (rc == PBS_OK)
         ok(hipMemcpyAsync(d_bounds, bounds, 2 * n * 8, hipMemcpyHostToDevice, st)) &&
@@ -3726,7 +3739,7 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
             }
         }
         hipLaunchKernelGGL(zstd_frame_sizes_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st,
-                           d_bounds, d_first, d_sizes, (uint64_t)n, compress, d_bsz, d_comp);
+                           d_bounds, d_first, d_sizes, (uint64_t)n, compress, d_bsz, d_comp, hdr);
         ok(hipGetLastError()) && ok(exclusive_sum_u64(d_tmp, &tmpb, d_bsz, d_boff,
                                                       (uint32_t)(n + 1), st)) &&
             (!compress ||
@@ -3739,11 +3752,16 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
     if (rc == PBS_OK) {
         hipLaunchKernelGGL(zstd_assemble_kernel, dim3((unsigned)std::min<uint64_t>(ni, (uint64_t)ncu * 8)),
                            dim3(kZThreads), 0, st, dev_data, base, d_bounds, d_items, ni, d_first, z_slots,
-                           d_sizes, d_ipre, d_boff, d_comp, blobs_dev);
+                           d_sizes, d_ipre, d_boff, d_comp, blobs_dev, hdr);
         ok(hipGetLastError()) && ok(hipEventRecord(ev[2], st));
     }
+    if (rc == PBS_OK && cfg) {  // AES-256-GCM in place, IV and tag into the headers
+        const int r = gcm_encrypt_blobs(cfg, blobs_dev, blob_offsets, d_boff, n, ivs, *ar, kZsGcm, gcm_host, st);
+        if (r != PBS_OK) fail(r);
+        else ok(hipEventRecord(ev[4], st));
+    }
     if (rc == PBS_OK) {
-        const hipError_t e = launch_crc32_skip(blobs_dev, d_boff, n, 12, d_crc, st);
+        const hipError_t e = launch_crc32_skip(blobs_dev, d_boff, n, hdr, d_crc, st);
         if (e != hipSuccess) fail(e == hipErrorOutOfMemory ? PBS_ERR_NOMEM : PBS_ERR_HIP);
     }
     if (rc == PBS_OK) {
@@ -3758,7 +3776,13 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
         float a = 0, b = 0, c = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        (void)hipEventElapsedTime(&c, ev[2], ev[3]);
+        (void)hipEventElapsedTime(&c, ev[cfg ? 4 : 2], ev[3]);
+        if (cfg && ct) {
+            float x = 0;
+            (void)hipEventElapsedTime(&x, ev[2], ev[4]);
+            ct->encrypt_ms = x;
+            ct->gcm_segments = gcm_host.segments;
+        }
         timing->compress_ms = a;
         timing->assemble_ms = b;
         timing->crc_ms = c;
@@ -3771,6 +3795,51 @@ extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data
     if (rc != PBS_OK) (void)hipStreamSynchronize(st);  // the arena goes back idle
     if (timing) timing->total_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
     return rc;
+}
+
+extern "C" int pbs_blob_encode_spans_device(const uint8_t* dev_data, size_t data_len, uint64_t base,
+                                            const uint64_t* spans, size_t n, int compress, uint8_t* blobs_dev,
+                                            size_t blobs_cap, uint64_t* blob_offsets, uint32_t* crcs,
+                                            uint8_t* compressed, pbs_blob_encode_timing* timing,
+                                            void* hip_stream) {
+    return encode_spans(dev_data, data_len, base, spans, n, compress, nullptr, nullptr, blobs_dev, blobs_cap,
+                        blob_offsets, crcs, compressed, timing, nullptr, hip_stream);
+}
+
+extern "C" int pbs_blob_encode_spans_encrypted_device(const uint8_t* dev_data, size_t data_len, uint64_t base,
+                                                      const uint64_t* spans, size_t n, int compress,
+                                                      const pbs_crypt_config* cfg, const uint8_t* ivs,
+                                                      uint8_t* blobs_dev, size_t blobs_cap, uint64_t* blob_offsets,
+                                                      uint32_t* crcs, uint8_t* compressed,
+                                                      pbs_blob_encode_timing_crypt* timing, void* hip_stream) {
+    if (timing) std::memset(timing, 0, sizeof(*timing));
+    if (!cfg) return PBS_ERR_ARG;
+    // (the compressed flags feed timing->base.compressed_chunks)
+    std::vector<uint8_t> comp_tmp;
+    if (timing && !compressed && n) {
+        comp_tmp.resize(n);
+        compressed = comp_tmp.data();
+    }
+    return encode_spans(dev_data, data_len, base, spans, n, compress, cfg, ivs, blobs_dev, blobs_cap, blob_offsets,
+                        crcs, compressed, timing ? &timing->base : nullptr, timing, hip_stream);
+}
+
+extern "C" int pbs_blob_encode_chunks_encrypted_device(const uint8_t* dev_data, size_t data_len, uint64_t base,
+                                                       const uint64_t* bounds, size_t n, int compress,
+                                                       const pbs_crypt_config* cfg, const uint8_t* ivs,
+                                                       uint8_t* blobs_dev, size_t blobs_cap, uint64_t* blob_offsets,
+                                                       uint32_t* crcs, uint8_t* compressed,
+                                                       pbs_blob_encode_timing_crypt* timing, void* hip_stream) {
+    if (timing) std::memset(timing, 0, sizeof(*timing));
+    if (!cfg || !blob_offsets || (n && !bounds)) return PBS_ERR_ARG;
+    std::vector<uint64_t> spans(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        spans[2 * i] = bounds[i];
+        spans[2 * i + 1] = bounds[i + 1];
+    }
+    return pbs_blob_encode_spans_encrypted_device(dev_data, data_len, base, spans.data(), n, compress, cfg, ivs,
+                                                  blobs_dev, blobs_cap, blob_offsets, crcs, compressed, timing,
+                                                  hip_stream);
 }
 
 extern "C" int pbs_blob_encode_chunks_device(const uint8_t* dev_data, size_t data_len, uint64_t base,

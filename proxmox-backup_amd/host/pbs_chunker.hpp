@@ -9,6 +9,8 @@
 //   pbs::sha256             openssl::sha::sha256 (host; index checksum)
 //   pbs::crc32_chunks_device DataBlob::compute_crc (data_blob.rs:70-75) per chunk, GPU
 //   pbs::crc32 / pbs::blob_encode_uncompressed  crc32fast::Hasher, DataBlob::encode(.., false)
+//   pbs::CryptConfig / pbs::blob_encode_chunks_encrypted_device  CryptConfig::new,
+//                           DataBlob::encode(.., Some(config), ..) per chunk, AES-256-GCM on the GPU
 //   pbs::digest_chunks_host  the per-chunk digest on host cores (SHA extensions)
 //   pbs::pipeline_host      ChunkStream + the upload stream's per-chunk digest
 //                           (chunk_stream.rs:40-77, backup_writer.rs:671-678) over a host buffer
@@ -269,6 +271,66 @@ inline std::vector<uint8_t> blob_encode_uncompressed(const uint8_t* data, size_t
     if (pbs_blob_encode_uncompressed(data, len, crc, out.data(), out.size()) != out.size())
         throw std::invalid_argument("data blob too large (" + std::to_string(len) + " bytes).");
     return out;
+}
+
+// CryptConfig::new(enc_key) (pbs-tools/src/crypt_config.rs:42-61): owns the C handle; the key
+// material is zeroed when it goes out of scope.  id_key() is the digest key of an encrypted
+// backup (pass it as `key` to the digest calls above).
+class CryptConfig {
+  public:
+    explicit CryptConfig(const std::array<uint8_t, 32>& enc_key) {
+        const int rc = pbs_crypt_config_new(enc_key.data(), &h_);
+        if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_crypt_config_new: ") + pbs_strerror(rc));
+    }
+    ~CryptConfig() { pbs_crypt_config_free(h_); }
+    CryptConfig(const CryptConfig&) = delete;
+    CryptConfig& operator=(const CryptConfig&) = delete;
+    const pbs_crypt_config* handle() const { return h_; }
+    std::vector<uint8_t> id_key() const {
+        const uint8_t* k = pbs_crypt_config_id_key(h_);
+        return std::vector<uint8_t>(k, k + 32);
+    }
+    // AES-256-GCM of `data` under a 16-byte IV on the host: ciphertext, and the tag in `tag`
+    std::vector<uint8_t> encrypt_host(const std::array<uint8_t, 16>& iv, const uint8_t* data, size_t len,
+                                      std::array<uint8_t, 16>& tag) const {
+        std::vector<uint8_t> out(len);
+        const int rc = pbs_aes256gcm_encrypt_host(h_, iv.data(), data, len, out.data(), tag.data());
+        if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_aes256gcm_encrypt_host: ") + pbs_strerror(rc));
+        return out;
+    }
+
+  private:
+    pbs_crypt_config* h_ = nullptr;
+};
+
+// DataBlob::encode(chunk, Some(config), compress) of every chunk [bounds[i], bounds[i+1]) of a
+// device-resident stream, on the GPU (pbs_blob_encode_chunks_encrypted_device): the blobs
+// back to back at `blobs_dev` (blobs_cap >= pbs_blob_stream_bound_encrypted), blob i at
+// [offsets[i], offsets[i+1]).  `ivs` empty: the library draws a fresh IV per blob; 16 n bytes:
+// the caller's IVs, for reproducible tests only -- reusing an IV under one key breaks GCM.
+struct EncryptedBlobs {
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> crcs;
+    std::vector<uint8_t> compressed;
+    pbs_blob_encode_timing_crypt timing;
+};
+inline EncryptedBlobs blob_encode_chunks_encrypted_device(const uint8_t* dev, size_t len, uint64_t base,
+                                                          const std::vector<uint64_t>& bounds, bool compress,
+                                                          const CryptConfig& crypt, uint8_t* blobs_dev,
+                                                          size_t blobs_cap, const std::vector<uint8_t>& ivs = {},
+                                                          void* hip_stream = nullptr) {
+    const size_t n = bounds.size() > 1 ? bounds.size() - 1 : 0;
+    if (!ivs.empty() && ivs.size() != 16 * n) throw std::invalid_argument("ivs must hold 16 bytes per chunk");
+    EncryptedBlobs r;
+    r.offsets.assign(n + 1, 0);
+    r.crcs.resize(n);
+    r.compressed.resize(n);
+    const int rc = pbs_blob_encode_chunks_encrypted_device(
+        dev, len, base, bounds.data(), n, compress ? 1 : 0, crypt.handle(), ivs.empty() ? nullptr : ivs.data(),
+        blobs_dev, blobs_cap, r.offsets.data(), r.crcs.data(), r.compressed.data(), &r.timing, hip_stream);
+    if (rc != PBS_OK)
+        throw std::runtime_error(std::string("pbs_blob_encode_chunks_encrypted_device: ") + pbs_strerror(rc));
+    return r;
 }
 
 // SHA-256 of every chunk [bounds[i], bounds[i+1]) of a host buffer (stream bytes

@@ -62,6 +62,10 @@ EXPORTED_SYMBOLS = (
     "pbs_blob_encode_chunks_device", "pbs_blob_stream_bound", "pbs_zstd_frame_bound",
     "pbs_blob_encode_release", "pbs_digest_hybrid_release", "pbs_debug_arena_allocs",
     "pbs_pipeline_release", "pbs_blob_encode_spans_device", "pbs_upload_stream_host",
+    # encrypted blobs (include/pbs_blob.h: crypt config, AES-256-GCM)
+    "pbs_crypt_config_new", "pbs_crypt_config_id_key", "pbs_crypt_config_free", "pbs_aes256gcm_encrypt_host",
+    "pbs_blob_encode_chunks_encrypted_device", "pbs_blob_encode_spans_encrypted_device",
+    "pbs_blob_stream_bound_encrypted", "pbs_upload_stream_host_crypt",
 )
 
 
@@ -113,6 +117,16 @@ class BlobEncodeTiming(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BlobEncodeTimingCrypt(ctypes.Structure):
+    _fields_ = [("base", BlobEncodeTiming), ("encrypt_ms", ctypes.c_double), ("gcm_segments", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = self.base.as_dict()
+        d["encrypt_ms"] = self.encrypt_ms
+        d["gcm_segments"] = self.gcm_segments
+        return d
 
 
 class UploadTiming(ctypes.Structure):
@@ -216,6 +230,18 @@ def lib():
         "pbs_upload_stream_host": ([sz, p, sz, sz, p, sz, i, p, sz, i, p, p, p, sz, ctypes.POINTER(sz),
                                     p, sz, p, p, ctypes.POINTER(UploadTiming)], i),
         "pbs_blob_stream_bound": ([p, sz], sz),
+        "pbs_crypt_config_new": ([p, ctypes.POINTER(p)], i),
+        "pbs_crypt_config_id_key": ([p], p),
+        "pbs_crypt_config_free": ([p], None),
+        "pbs_aes256gcm_encrypt_host": ([p, p, p, sz, p, p], i),
+        "pbs_blob_encode_chunks_encrypted_device": ([p, sz, u64, p, sz, i, p, p, p, sz, p, p, p,
+                                                     ctypes.POINTER(BlobEncodeTimingCrypt), p], i),
+        "pbs_blob_encode_spans_encrypted_device": ([p, sz, u64, p, sz, i, p, p, p, sz, p, p, p,
+                                                    ctypes.POINTER(BlobEncodeTimingCrypt), p], i),
+        "pbs_blob_stream_bound_encrypted": ([p, sz], sz),
+        "pbs_upload_stream_host_crypt": ([sz, p, sz, sz, p, i, p, sz, i, p, p, p, sz, ctypes.POINTER(sz),
+                                          p, sz, p, p, ctypes.POINTER(UploadTiming),
+                                          ctypes.POINTER(ctypes.c_double)], i),
         "pbs_zstd_frame_bound": ([sz], sz),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
@@ -225,6 +251,7 @@ def lib():
         "pbs_test_scan_main_plan": ([u64, i, ctypes.POINTER(u64)], i),
         "pbs_test_set_fused_epoch": ([p, ctypes.c_uint32], i),
         "pbs_test_handle_stats": ([p, ctypes.POINTER(u64)], i),
+        "pbs_test_gcm_tag_segments_host": ([p, p, p, sz, p], i),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("PBS_LIBPBSCHUNK_AB") and not hasattr(L, name):
@@ -688,16 +715,107 @@ def crc32_chunks_device(dev_ptr: int, data_len: int, bounds, base: int = 0, hip_
     return out
 
 
+BLOB_HEADER_SIZE = 12
+BLOB_ENC_HEADER_SIZE = 44  # EncryptedDataBlobHeader
+GCM_SEGMENT_BYTES = 65536  # PBS_GCM_SEGMENT_BYTES: one workgroup's share of a payload
+
+
+class CryptConfig:
+    """`CryptConfig::new(enc_key)` (pbs-tools/src/crypt_config.rs:42-61): the handle the
+    encrypted blob calls take.  ``id_key`` is the key appended to every chunk's digest
+    message.  ``close()`` (or leaving a ``with`` block) zeroes and frees the key material."""
+
+    def __init__(self, enc_key):
+        k = bytes(enc_key)
+        if len(k) != 32:
+            raise ValueError("the encryption key must be 32 bytes")
+        h = ctypes.c_void_p()
+        rc = lib().pbs_crypt_config_new(ctypes.create_string_buffer(k, 32), ctypes.byref(h))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_crypt_config_new")
+        self._h = h
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise RuntimeError("crypt config is closed")
+        return self._h
+
+    @property
+    def id_key(self) -> bytes:
+        return ctypes.string_at(lib().pbs_crypt_config_id_key(self.handle), 32)
+
+    def encrypt_host(self, iv, data):
+        """pbs_aes256gcm_encrypt_host: (ciphertext, tag) of ``data`` under a 16-byte IV."""
+        ivb = bytes(iv)
+        if len(ivb) != 16:
+            raise ValueError("the IV must be 16 bytes")
+        a = _as_u8(data)
+        out = np.empty(a.size, dtype=np.uint8)
+        tag = (ctypes.c_uint8 * 16)()
+        rc = lib().pbs_aes256gcm_encrypt_host(self.handle, ctypes.create_string_buffer(ivb, 16), _ptr(a), a.size,
+                                              _ptr(out), tag)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_aes256gcm_encrypt_host")
+        return out.tobytes(), bytes(tag)
+
+    def close(self):
+        if self._h is not None:
+            lib().pbs_crypt_config_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _ivs_arg(ivs, n: int):
+    """(keep-alive array, pointer) of n caller-supplied 16-byte IVs, or (None, None): the
+    library draws them.  Caller-supplied IVs are for reproducible tests only -- reusing an
+    IV under one key breaks GCM."""
+    if ivs is None:
+        return None, None
+    a = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for x in ivs), dtype=np.uint8)
+                             if isinstance(ivs, (list, tuple)) else np.asarray(ivs, dtype=np.uint8)).reshape(-1)
+    if a.size != 16 * n:
+        raise ValueError(f"ivs holds {a.size} bytes, {n} blobs need {16 * n}")
+    return a, (a.ctypes.data if a.size else None)
+
+
 def blob_encode_chunks_device(dev_ptr: int, data_len: int, bounds, blobs_dev: int, blobs_cap: int,
-                              base: int = 0, compress: bool = True, hip_stream: int = 0):
+                              base: int = 0, compress: bool = True, hip_stream: int = 0,
+                              crypt=None, ivs=None):
     """pbs_blob_encode_chunks_device: the DataBlob image of every chunk written back to
     back at device address blobs_dev (data_blob.rs:87-176; zstd frames where shorter).
-    Returns (offsets (n + 1), crcs (n), compressed flags (n), timing dict)."""
+    Returns (offsets (n + 1), crcs (n), compressed flags (n), timing dict).
+    ``crypt`` (a CryptConfig): encrypted blobs (pbs_blob_encode_chunks_encrypted_device;
+    44-byte headers, blobs_cap >= blob_stream_bound_encrypted); ``ivs``: None -- the library
+    draws a fresh IV per blob -- or n 16-byte IVs, for reproducible tests only."""
     b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
     n = max(0, b.size - 1)
     offs = np.zeros(n + 1, dtype=np.uint64)
     crcs = np.empty(n, dtype=np.uint32)
     comp = np.empty(n, dtype=np.uint8)
+    if crypt is not None:
+        iva, ivp = _ivs_arg(ivs, n)
+        tc = BlobEncodeTimingCrypt()
+        rc = lib().pbs_blob_encode_chunks_encrypted_device(
+            ctypes.c_void_p(dev_ptr), data_len, base, b.ctypes.data, n, 1 if compress else 0, crypt.handle, ivp,
+            ctypes.c_void_p(blobs_dev), blobs_cap, offs.ctypes.data, crcs.ctypes.data, comp.ctypes.data,
+            ctypes.byref(tc), ctypes.c_void_p(hip_stream))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_blob_encode_chunks_encrypted_device")
+        return offs, crcs, comp, tc.as_dict()
+    if ivs is not None:
+        raise ValueError("ivs without crypt")
     t = BlobEncodeTiming()
     rc = lib().pbs_blob_encode_chunks_device(ctypes.c_void_p(dev_ptr), data_len, base, b.ctypes.data, n,
                                              1 if compress else 0, ctypes.c_void_p(blobs_dev), blobs_cap,
@@ -709,15 +827,29 @@ def blob_encode_chunks_device(dev_ptr: int, data_len: int, bounds, blobs_dev: in
 
 
 def blob_encode_spans_device(dev_ptr: int, data_len: int, spans, blobs_dev: int, blobs_cap: int,
-                             base: int = 0, compress: bool = True, hip_stream: int = 0):
+                             base: int = 0, compress: bool = True, hip_stream: int = 0,
+                             crypt=None, ivs=None):
     """pbs_blob_encode_spans_device: as blob_encode_chunks_device for chunks given as
     (start, end) absolute spans in any order (e.g. an upload's new chunks); blob i is
-    written for span i.  Returns (offsets (n + 1), crcs (n), compressed flags (n), timing)."""
+    written for span i.  Returns (offsets (n + 1), crcs (n), compressed flags (n), timing).
+    ``crypt`` / ``ivs``: as blob_encode_chunks_device."""
     sp = np.ascontiguousarray(np.asarray(spans, dtype=np.uint64).reshape(-1, 2))
     n = sp.shape[0]
     offs = np.zeros(n + 1, dtype=np.uint64)
     crcs = np.empty(n, dtype=np.uint32)
     comp = np.empty(n, dtype=np.uint8)
+    if crypt is not None:
+        iva, ivp = _ivs_arg(ivs, n)
+        tc = BlobEncodeTimingCrypt()
+        rc = lib().pbs_blob_encode_spans_encrypted_device(
+            ctypes.c_void_p(dev_ptr), data_len, base, sp.ctypes.data, n, 1 if compress else 0, crypt.handle, ivp,
+            ctypes.c_void_p(blobs_dev), blobs_cap, offs.ctypes.data, crcs.ctypes.data, comp.ctypes.data,
+            ctypes.byref(tc), ctypes.c_void_p(hip_stream))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_blob_encode_spans_encrypted_device")
+        return offs, crcs, comp, tc.as_dict()
+    if ivs is not None:
+        raise ValueError("ivs without crypt")
     t = BlobEncodeTiming()
     rc = lib().pbs_blob_encode_spans_device(ctypes.c_void_p(dev_ptr), data_len, base, sp.ctypes.data, n,
                                             1 if compress else 0, ctypes.c_void_p(blobs_dev), blobs_cap,
@@ -752,6 +884,12 @@ def pipeline_release() -> None:
 def blob_stream_bound(bounds) -> int:
     b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
     return int(lib().pbs_blob_stream_bound(b.ctypes.data, max(0, b.size - 1)))
+
+
+def blob_stream_bound_encrypted(bounds) -> int:
+    """44 n + the chunks' bytes: the largest encrypted blob stream of n chunks."""
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.uint64))
+    return int(lib().pbs_blob_stream_bound_encrypted(b.ctypes.data, max(0, b.size - 1)))
 
 
 def crc32_chunks_async(dev_ptr: int, data_len: int, bounds_dev: int, order_dev: int, n: int, crcs_dev: int,
@@ -880,7 +1018,7 @@ def index_stream_device(chunker: "Chunker", dev_ptr: int, length: int, key=None,
 
 def upload_stream_host(data, avg: int, known=None, key=None, piece: int = 1 << 30,
                        uuid: bytes = bytes(16), ctime: int = 0, compress: bool = True,
-                       digest_cus: int = 64, blobs_out=None) -> dict:
+                       digest_cus: int = 64, blobs_out=None, crypt=None) -> dict:
     """The client's upload of one dynamic-index stream from a host buffer, up to the
     network (pbs-client/src/backup_writer.rs:631-706 upload_chunk_info_stream; the client
     backs up with compress = true, proxmox-backup-client/src/main.rs:1011-1016): chunk
@@ -894,7 +1032,10 @@ def upload_stream_host(data, avg: int, known=None, key=None, piece: int = 1 << 3
     blobs[blob_offsets[i]:blob_offsets[i + 1]], empty for a known chunk), blob_offsets
     (n + 1), compressed (n flags), new_chunks = [(start, length), ...], stats (UploadStats,
     backup_writer.rs:56-64) and timing.
-    ``blobs_out``: an optional preallocated uint8 array (e.g. pinned) for the blobs."""
+    ``blobs_out``: an optional preallocated uint8 array (e.g. pinned) for the blobs.
+    ``crypt`` (a CryptConfig): an encrypted backup (pbs_upload_stream_host_crypt) -- the
+    digests are SHA-256(chunk || id_key) (``key`` must then be None) and every new chunk is
+    an AES-256-GCM blob with a library-drawn IV; timing gains ``encrypt_ms``."""
     a = _as_u8(data)
     cap = a.size // max(int(avg) >> 2, 65) + 4
     ends = np.empty(cap, dtype=np.uint64)
@@ -902,7 +1043,9 @@ def upload_stream_host(data, avg: int, known=None, key=None, piece: int = 1 << 3
     is_known = np.empty(cap, dtype=np.uint8)
     offs = np.zeros(cap + 1, dtype=np.uint64)
     comp = np.empty(cap, dtype=np.uint8)
-    bcap = 12 * cap + a.size
+    if crypt is not None and key is not None:
+        raise ValueError("crypt brings its own digest key (id_key)")
+    bcap = (BLOB_ENC_HEADER_SIZE if crypt is not None else BLOB_HEADER_SIZE) * cap + a.size
     blobs = blobs_out if blobs_out is not None else np.empty(max(bcap, 1), dtype=np.uint8)
     if blobs.size < bcap:
         raise ValueError(f"blobs_out holds {blobs.size} bytes, the stream needs up to {bcap}")
@@ -912,19 +1055,30 @@ def upload_stream_host(data, avg: int, known=None, key=None, piece: int = 1 << 3
     kb, kl = _key_arg(key)
     n = ctypes.c_size_t(0)
     t = UploadTiming()
-    rc = lib().pbs_upload_stream_host(avg, _ptr(a), a.size, piece, kb, kl, digest_cus,
-                                      kd.ctypes.data if kd.size else None, kd.shape[0], 1 if compress else 0,
-                                      ends.ctypes.data, dig.ctypes.data, is_known.ctypes.data, cap,
-                                      ctypes.byref(n), blobs.ctypes.data, blobs.size, offs.ctypes.data,
-                                      comp.ctypes.data, ctypes.byref(t))
+    enc_ms = ctypes.c_double(0.0)
+    if crypt is not None:
+        rc = lib().pbs_upload_stream_host_crypt(avg, _ptr(a), a.size, piece, crypt.handle, digest_cus,
+                                                kd.ctypes.data if kd.size else None, kd.shape[0],
+                                                1 if compress else 0, ends.ctypes.data, dig.ctypes.data,
+                                                is_known.ctypes.data, cap, ctypes.byref(n), blobs.ctypes.data,
+                                                blobs.size, offs.ctypes.data, comp.ctypes.data, ctypes.byref(t),
+                                                ctypes.byref(enc_ms))
+    else:
+        rc = lib().pbs_upload_stream_host(avg, _ptr(a), a.size, piece, kb, kl, digest_cus,
+                                          kd.ctypes.data if kd.size else None, kd.shape[0], 1 if compress else 0,
+                                          ends.ctypes.data, dig.ctypes.data, is_known.ctypes.data, cap,
+                                          ctypes.byref(n), blobs.ctypes.data, blobs.size, offs.ctypes.data,
+                                          comp.ctypes.data, ctypes.byref(t))
     if rc != PBS_OK:
-        raise ChunkerError(rc, "pbs_upload_stream_host")
+        raise ChunkerError(rc, "pbs_upload_stream_host_crypt" if crypt is not None else "pbs_upload_stream_host")
     m = n.value
     ends, dig, is_known, offs, comp = ends[:m].copy(), dig[:m].copy(), is_known[:m].copy(), offs[:m + 1].copy(), comp[:m].copy()
     image, csum = didx_build(ends, dig, uuid, ctime)
     starts = np.concatenate([[0], ends[:-1]]).astype(np.uint64) if m else np.zeros(0, np.uint64)
     new = [(int(starts[i]), int(ends[i] - starts[i])) for i in np.flatnonzero(is_known == 0)]
     td = t.as_dict()
+    if crypt is not None:
+        td["encrypt_ms"] = enc_ms.value
     stats = {k: td[k] for k in ("chunk_count", "chunk_reused", "size", "size_reused", "size_compressed")}
     return {"ends": ends, "digests": dig, "known": is_known, "csum": csum, "didx": image,
             "blobs": blobs[:int(offs[-1])] if m else blobs[:0], "blob_offsets": offs, "compressed": comp,

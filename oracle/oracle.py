@@ -275,6 +275,8 @@ def _twin_lib():
         L.zstd_twin_bound.argtypes = [ctypes.c_uint64]
         L.zstd_twin_frame.restype = ctypes.c_uint64
         L.zstd_twin_frame.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.zstd_twin_parse.restype = ctypes.c_uint64
+        L.zstd_twin_parse.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
         _twin = L
     return _twin
 
@@ -286,6 +288,27 @@ def zstd_twin_frame(chunk) -> bytes:
     out = np.empty(int(L.zstd_twin_bound(a.size)) + 16, dtype=np.uint8)
     n = L.zstd_twin_frame(a.ctypes.data if a.size else None, a.size, out.ctypes.data)
     return out[:n].tobytes()
+
+
+def zstd_twin_bound(size: int) -> int:
+    """The largest frame the twin (and the GPU encoder) writes for a chunk of `size` bytes."""
+    return int(_twin_lib().zstd_twin_bound(int(size)))
+
+
+def zstd_twin_parse(block, history=b"") -> np.ndarray:
+    """The twin's parse of one block (at most 64 KiB) that follows the chunk bytes `history`
+    (all of the chunk before the block): an (n, 3) uint32 array of {pos, ml, off} -- match
+    start as a block position, length, offset -- in the order the encoder emits them."""
+    hist = np.frombuffer(bytes(history), dtype=np.uint8)
+    blk = np.frombuffer(bytes(block), dtype=np.uint8)
+    assert 0 < blk.size <= 64 * 1024, blk.size
+    a = np.ascontiguousarray(np.concatenate([hist, blk]))
+    L = _twin_lib()
+    cap = blk.size // 5 + 32
+    out = np.empty((cap, 3), dtype=np.uint32)
+    n = int(L.zstd_twin_parse(a.ctypes.data + hist.size, blk.size, hist.size, out.ctypes.data, cap))
+    assert n <= cap, (n, cap)
+    return out[:n].copy()
 
 
 def libzstd():

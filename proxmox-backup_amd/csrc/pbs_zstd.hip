@@ -10,8 +10,8 @@
 //   stage   the block and up to 16 KiB of the chunk before it (the match window of its
 //           first sub-blocks) in LDS -- every later byte read is LDS;
 //   RLE     every byte equal: a 4-byte RLE block (the zero pages of a VM image);
-//   parse   each of the 8 waves parses one ~8 KiB sub-block (8 KiB + 384 bytes for waves
-//           0-3, - 384 for waves 4-7: see kZSubA) with its own 4096-entry table
+//   parse   each of the 8 waves parses one ~8 KiB sub-block (8 KiB + 768 bytes for waves
+//           0-3, - 768 for waves 4-7: see kZSubA) with its own 4096-entry table
 //           of 16-bit window positions: the 12 KiB before the sub-block first enter the
 //           table in accelerated rounds (every 2nd position or sparser), then rounds of
 //           256 sampled positions (step 1

@@ -174,12 +174,6 @@ __device__ __forceinline__ void tab_max(lds_u16* e, uint32_t v) {
 // a wave complete in issue order), then the rare retries
 template <int K>
 __device__ __forceinline__ void tab_max_batch(lds_u16* tw, const uint32_t* h, const uint32_t* v, const bool* ok) {
-#if PBS_ZV_SERIALTAB
-#pragma unroll
-    for (int i = 0; i < K; ++i)
-        if (ok[i]) tab_max(&tw[h[i]], v[i]);
-    return;
-#endif
     volatile lds_u16* const base = tw;
 #pragma unroll
     for (int i = 0; i < K; ++i)
@@ -276,67 +270,6 @@ __device__ __forceinline__ void stage_to_global(uint8_t* dst, const Win& W, uint
     }
     for (uint32_t i = head + 4 * nwd + t; i < cnt; i += nt) dst[i] = (uint8_t)W.byte(from + i);
 }
-
-// ---------------------------------------------------------------- bit writers
-// Backward bit stream of RFC 8878 4.1 as an encoder writes it (fields at increasing bit
-// positions, bytes little-endian), one lane, to global memory.
-struct GBits {
-    uint64_t acc;
-    uint32_t n;
-    uint8_t* p;
-    __device__ void init(uint8_t* dst) {
-        acc = 0;
-        n = 0;
-        p = dst;
-    }
-    __device__ void put(uint64_t v, uint32_t nb) {
-        acc |= (v & ((1ull << nb) - 1ull)) << n;  // nb <= 32
-        n += nb;
-        if (n >= 32) {
-            p[0] = (uint8_t)acc;
-            p[1] = (uint8_t)(acc >> 8);
-            p[2] = (uint8_t)(acc >> 16);
-            p[3] = (uint8_t)(acc >> 24);
-            p += 4;
-            acc >>= 32;
-            n -= 32;
-        }
-    }
-    __device__ void close() {
-        put(1, 1);
-        while (n > 0) {
-            *p++ = (uint8_t)acc;
-            acc >>= 8;
-            n = n > 8 ? n - 8 : 0;
-        }
-    }
-};
-
-// the same into an LDS byte buffer (weights description)
-struct LBits {
-    uint64_t acc;
-    uint32_t n;
-    uint8_t* p;
-    __device__ void init(uint8_t* dst) {
-        acc = 0;
-        n = 0;
-        p = dst;
-    }
-    __device__ void put(uint64_t v, uint32_t nb) {
-        acc |= (v & ((1ull << nb) - 1ull)) << n;
-        n += nb;
-        while (n >= 8) {
-            *p++ = (uint8_t)acc;
-            acc >>= 8;
-            n -= 8;
-        }
-    }
-    __device__ void close() {
-        put(1, 1);
-        if (n) *p++ = (uint8_t)acc;
-        n = 0;
-    }
-};
 
 // ---------------------------------------------------------------- FSE (one lane)
 constexpr int kFseCells = 512;
@@ -508,12 +441,6 @@ __device__ __forceinline__ uint32_t fse_init(const FseView& t, uint32_t s) {
     const uint32_t nb = (uint32_t)((t.dnb[s] + (1 << 15)) >> 16);
     const uint32_t v0 = (nb << 16) - (uint32_t)t.dnb[s];
     return t.next[(v0 >> nb) + t.dfs[s]];
-}
-template <typename B>
-__device__ __forceinline__ void fse_enc(B& b, const FseView& t, uint32_t& v, uint32_t s) {
-    const uint32_t nb = (v + (uint32_t)t.dnb[s]) >> 16;
-    b.put(v, nb);
-    v = t.next[(v >> nb) + t.dfs[s]];
 }
 
 __device__ __noinline__ int fse_log(uint32_t total, uint32_t max_sym, int max_log) {
@@ -691,29 +618,35 @@ __device__ __noinline__ void seq_table_wave(FseT& t, const uint32_t* cnt, int ns
 }
 
 // ---------------------------------------------------------------- LDS layout
-// work area (64 KiB): the parse's tables, then the entropy stage's buffers
-struct EntropyArea {
-    uint32_t streams[kHufStreams / 4 + 4];  // Huffman streams (and, before them, per-wave literal histograms)
-    uint32_t bitmap[kEncBlock / 32];        // literal bytes of the block
-    uint32_t hist[256];
-    uint32_t keys[256];   // symbols sorted by (count, symbol)
-    uint32_t tw[512];     // Huffman merge: node weights
-    uint16_t par[512];    // ... and parents
-    uint8_t lens[256];    // code length per sorted index
-    uint8_t len[256];     // code length per symbol
+// The entropy kernel's buffers (the parse kernel's, PArea and PCtl, stand beside it).  The
+// stream buffer is 36.5 KiB: Huffman streams (up to kHufStreams, 48 KiB) longer than it are
+// ORed into the output in global memory instead (same bytes), and so is a sequence bit
+// stream longer than it; with it three workgroups fit a CU's LDS.
+constexpr uint32_t kEStreams = 36 * 1024 + 512;  // (3 x the LDS of a workgroup must stay under 160 KiB after the allocation granule)
+struct EArea {
+    // the Huffman merge's scratch (keys, tw, par: literal_mode_wave only) shares the stream
+    // buffer, which is free until the literal section
+    union {
+        uint32_t streams[kEStreams / 4 + 4];
+        struct {
+            uint32_t keys[256];  // symbols sorted by (count, symbol)
+            uint32_t tw[512];    // Huffman merge: node weights
+            uint16_t par[512];   // ... and parents
+        };
+    };
+    uint32_t hist[256];  // literal histogram
+    uint8_t lens[256];   // code length per sorted index
+    uint8_t len[256];    // code length per symbol
     uint16_t code[256];
     uint32_t shist[36 + 53 + 32];  // sequence code histograms: LL, ML, OF
 };
-static_assert(sizeof(EntropyArea) <= 64 * 1024, "entropy buffers fit the work area");
 
 struct Ctl {
     uint32_t nseq[kZWaves];     // sequences per sub-block
-    uint32_t lastend[kZWaves];  // end of the sub-block's last match (block position), 0 if none
     uint32_t wsum[kZWaves];     // block-scan partials
     uint32_t wsum2[kZWaves];
     uint32_t segP[5];           // Huffman: bits before each segment boundary
-    uint32_t lit_mode, lit_size, huf_c, huf_hs, desc_len, need_full;
-    uint32_t run_start[kZRuns], run_len[kZRuns], run_out[kZRuns];  // literal runs of a block with few sequences
+    uint32_t lit_mode, lit_size, huf_c, huf_hs, desc_len;
     uint32_t seq_size, seq_ok, seq_hdr, seq_last[3];  // sequences: body size, fits, header bytes, final states
     int32_t root;               // Huffman merge: the root node
     uint8_t desc[264];          // Huffman tree description (FSE form: <= ~210 bytes before the 128 check)
@@ -745,8 +678,7 @@ __device__ __forceinline__ void wr_q(uint32_t (&r)[4], uint32_t i, uint32_t v) {
 // weights, the table (log <= 6: one cell per lane) and the output bytes live in registers,
 // so the serial encode is readlanes and scalar arithmetic (round 4's one-lane version
 // waited on LDS at every weight: ~40-60 us a block); counts and the direct form by lanes.
-template <class EA>
-__device__ __noinline__ bool huf_describe(EA& E, Ctl& ctl, FseT& t_scratch, uint32_t mb, uint32_t lastsym,
+__device__ __noinline__ bool huf_describe(EArea& E, Ctl& ctl, FseT& t_scratch, uint32_t mb, uint32_t lastsym,
                                           int lane) {
     const uint32_t nwt = uni(lastsym);
     uint32_t wreg[4], wmax = 0;  // weight of symbol lane + 64 j
@@ -1052,21 +984,6 @@ __device__ __noinline__ void seq_chain_wave(FseView t, const Coded* __restrict__
     const uint32_t lastlane = m ? (m - 1) / seg : 0;
     const uint32_t fin = (uint32_t)__shfl((int)end, (int)lastlane, 64);
     if (lane == 0) *last = m ? fin : x0;
-}
-
-// bits of sequence q in the stream: its three state fields (none for the last sequence,
-// nor for an RLE-mode stream) and its extra bits
-__device__ __forceinline__ uint32_t seq_bits(const Coded& x, uint32_t q, uint32_t ns, const uint32_t* chains,
-                                             uint32_t stride, const uint32_t* mode) {
-    const uint32_t llc = x.codes & 0xFF, mlc = (x.codes >> 8) & 0xFF, ofc = x.codes >> 16;
-    uint32_t b = ll_bits(llc) + ml_bits(mlc) + ofc;
-    if (q + 1 < ns) {
-        const uint32_t j = ns - 2 - q;  // the chains are in step order
-        if (mode[0] != 1) b += chains[j] >> 16;
-        if (mode[1] != 1) b += chains[stride + j] >> 16;
-        if (mode[2] != 1) b += chains[2 * stride + j] >> 16;
-    }
-    return b;
 }
 
 // a thread's bits into the zeroed stream words (atomicOr: its first and last words are
@@ -1529,8 +1446,7 @@ __device__ __noinline__ uint64_t parse_subblock(const Win W, lds_u16* __restrict
 // creation order, ties taking the leaf; parents in E.par, the root in ctl.root.  A step reads
 // the two heads of both queues at once (one LDS wait, not one per pop): the second pop
 // takes from these four; a head past its queue is read but not used.
-template <class EA>
-__device__ __noinline__ void huf_merge(EA& E, Ctl& ctl, uint32_t dist) {
+__device__ __noinline__ void huf_merge(EArea& E, Ctl& ctl, uint32_t dist) {
         const int m = (int)dist;
         int li = 0, ii = m, nn = m;
         while (nn < 2 * m - 1) {
@@ -1558,8 +1474,7 @@ __device__ __noinline__ void huf_merge(EA& E, Ctl& ctl, uint32_t dist) {
 // Literal section mode of a block (ONE WAVE): RLE (one distinct byte), raw, or Huffman
 // when the entropy estimate says it may pay -- then the code lengths (two-queue merge,
 // limited to 11 bits), canonical codes and the tree description.  ctl.lit_mode = lane 0's.
-template <class EA>
-__device__ __noinline__ void literal_mode_wave(EA& E, Ctl& ctl, FseT& fsc, uint32_t nlit, int lane,
+__device__ __noinline__ void literal_mode_wave(EArea& E, Ctl& ctl, FseT& fsc, uint32_t nlit, int lane,
                                                unsigned long long* probe) {
     uint64_t tq = probe ? wall_clock64() : 0;
     auto mark = [&](int idx) {
@@ -1734,118 +1649,6 @@ __device__ __noinline__ void literal_mode_wave(EA& E, Ctl& ctl, FseT& fsc, uint3
     if (lane == 0) ctl.lit_mode = mode;  // (lane 0's: it may have fallen back to raw)
 }
 
-// The literal section (all threads): Huffman streams ORed into LDS at offsets from the
-// block scan of code lengths and copied out, or raw bytes compacted through LDS, or the
-// RLE byte.  Thread t's literals are the set bits of bm (block positions 128 t ..).
-__device__ __noinline__ void write_literals(EntropyArea& E, const Ctl& ctl, const Win W, uint32_t hist, uint4 bm4,
-                                            uint32_t litbase, uint32_t bbase, uint32_t nlit, uint32_t lm, bool four,
-                                            uint32_t seg, uint8_t* lit_out, int tid, uint32_t nruns) {
-    const uint32_t bmw[4] = {bm4.x, bm4.y, bm4.z, bm4.w};
-    if (lm == 2) {
-        const uint32_t words = kHufStreams / 4 + 4;
-        for (uint32_t i = tid; i < words; i += kZThreads) E.streams[i] = 0;
-        __syncthreads();
-        // stream s starts at byte S_s of the LDS buffer
-        // (scalars, not an array: a dynamically indexed array would live in scratch memory)
-        const uint32_t S0 = 0;
-        const uint32_t S1 = four ? (ctl.segP[1] - ctl.segP[0] + 8) / 8 : (ctl.segP[4] - ctl.segP[0] + 8) / 8;
-        const uint32_t S2 = four ? S1 + (ctl.segP[2] - ctl.segP[1] + 8) / 8 : S1;
-        const uint32_t S3 = four ? S2 + (ctl.segP[3] - ctl.segP[2] + 8) / 8 : S1;
-        const uint32_t S4 = four ? S3 + (ctl.segP[4] - ctl.segP[3] + 8) / 8 : S1;
-        auto Sat = [&](uint32_t g) { return g == 0 ? S0 : g == 1 ? S1 : g == 2 ? S2 : g == 3 ? S3 : S4; };
-        uint32_t idx = litbase, pb = bbase;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            for (uint32_t m2 = bmw[i]; m2; m2 &= m2 - 1) {
-                const uint32_t sym = W.byte(hist + 128 * tid + 32 * i + __builtin_ctz(m2));
-                const uint32_t L = E.len[sym], cv = E.code[sym];
-                const uint32_t sg = four ? min(idx / seg, 3u) : 0u;
-                const uint32_t endP = four ? ctl.segP[sg + 1] : ctl.segP[4];
-                const uint32_t o = 8 * Sat(sg) + (endP - pb - L);
-                const uint64_t v = (uint64_t)cv << (o & 31);
-                atomicOr(&E.streams[o >> 5], (uint32_t)v);
-                if ((o & 31) + L > 32) atomicOr(&E.streams[(o >> 5) + 1], (uint32_t)(v >> 32));
-                pb += L;
-                ++idx;
-            }
-        if (tid < (four ? 4 : 1)) {  // end marks
-            const uint32_t bits = ctl.segP[four ? tid + 1 : 4] - ctl.segP[tid];
-            const uint32_t o = 8 * Sat((uint32_t)tid) + bits;
-            atomicOr(&E.streams[o >> 5], 1u << (o & 31));
-        }
-        __syncthreads();
-        const uint32_t hs = ctl.huf_hs, c = ctl.huf_c;
-        const uint32_t dl = ctl.desc_len;
-        uint8_t* const body = lit_out + hs;
-        if (tid == 0) {
-            if (hs == 3) {
-                const uint32_t v = 2u | (four ? 1u : 0u) << 2 | nlit << 4 | c << 14;
-                lit_out[0] = (uint8_t)v;
-                lit_out[1] = (uint8_t)(v >> 8);
-                lit_out[2] = (uint8_t)(v >> 16);
-            } else if (hs == 4) {
-                const uint32_t v = 2u | 2u << 2 | nlit << 4 | c << 18;
-                for (int i = 0; i < 4; ++i) lit_out[i] = (uint8_t)(v >> (8 * i));
-            } else {
-                const uint64_t v = 2u | 3u << 2 | (uint64_t)nlit << 4 | (uint64_t)c << 22;
-                for (int i = 0; i < 5; ++i) lit_out[i] = (uint8_t)(v >> (8 * i));
-            }
-            if (four)
-                for (int s = 0; s < 3; ++s) {
-                    const uint32_t sz = Sat((uint32_t)s + 1) - Sat((uint32_t)s);
-                    body[dl + 2 * s] = (uint8_t)sz;
-                    body[dl + 2 * s + 1] = (uint8_t)(sz >> 8);
-                }
-        }
-        for (uint32_t i = tid; i < dl; i += kZThreads) body[i] = ctl.desc[i];
-        const uint32_t tot = four ? S4 : S1;
-        lds_to_global(body + dl + (four ? 6 : 0), E.streams, tot, (uint32_t)tid, kZThreads);
-    } else {
-        const uint32_t rawh = nlit < 32 ? 1u : nlit < 4096 ? 2u : 3u;
-        if (tid == 0) {
-            const uint32_t t = lm;  // 0 raw, 1 RLE
-            if (rawh == 1) {
-                lit_out[0] = (uint8_t)(t | nlit << 3);
-            } else if (rawh == 2) {
-                lit_out[0] = (uint8_t)(t | 1u << 2 | nlit << 4);
-                lit_out[1] = (uint8_t)(nlit >> 4);
-            } else {
-                lit_out[0] = (uint8_t)(t | 3u << 2 | nlit << 4);
-                lit_out[1] = (uint8_t)(nlit >> 4);
-                lit_out[2] = (uint8_t)(nlit >> 12);
-            }
-        }
-        if (lm == 1) {
-            if (tid == 0) {  // the one distinct byte
-                uint32_t s = 0;
-                while (!E.hist[s]) ++s;
-                lit_out[rawh] = (uint8_t)s;
-            }
-        } else if (nruns) {
-            // few sequences: run by run, every thread on each run (coalesced dword stores)
-            for (uint32_t r = 0; r < nruns; ++r)
-                stage_to_global(lit_out + rawh + ctl.run_out[r], W, hist + ctl.run_start[r], ctl.run_len[r],
-                                (uint32_t)tid, kZThreads);
-        } else {
-            // compacted through LDS (the stream buffer, free here) in pieces of 48 KiB, then
-            // copied out with dword stores: scattered global byte stores cost a line each
-            uint8_t* const lb = reinterpret_cast<uint8_t*>(E.streams);
-            for (uint32_t pb = 0; pb < nlit; pb += kHufStreams) {
-                const uint32_t pe = min(nlit, pb + kHufStreams);
-                uint32_t idx = litbase;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    for (uint32_t m2 = bmw[i]; m2; m2 &= m2 - 1, ++idx)
-                        if (idx >= pb && idx < pe)
-                            lb[idx - pb] = (uint8_t)W.byte(hist + 128 * tid + 32 * i + __builtin_ctz(m2));
-                __syncthreads();
-                lds_to_global(lit_out + rawh + pb, E.streams, pe - pb, (uint32_t)tid, kZThreads);
-                __syncthreads();
-            }
-        }
-    }
-}
-
 // Repeat-offset coding of sub-block w2 by ONE WAVE (the repeat offsets are tracked per
 // sub-block): literal lengths, offset values, codes.  The offsets are a serial state
 // machine, but its state is the last three offsets, so it forgets its past: lane l codes
@@ -1949,17 +1752,24 @@ __device__ __noinline__ void rep_code_wave(const uint32_t* nseq, const uint32_t*
 }
 
 // PBS_ZSTD_PROBE=1 (diagnostics): workgroup 0, thread 0 adds the wall-clock ticks (100 MHz)
-// of each phase into g_zprobe: 0 stage + RLE, 1 parse, 2 literal bitmap + histogram,
-// 3 literal mode / Huffman code + repeat codes, 4 code histograms + Huffman sizes,
-// 5 sequence tables, 6 state chains + literal size, 7 literal section, 8 sequence bit
-// stream, 9 block end; 10 blocks, 11 sequences, 12 literals; 13/14 wave 0's history and
-// rounds + walk; 15 literal bitmap, 16 sampled histogram (both inside 2); per role (lane 0
-// of the wave doing it): 17 literal mode (wave 0), 18 repeat coding (wave 1), 19 LL table
-// (wave 1), 20 LL state chain (wave 1), 21 literal section (wave 0); long LL chains: 22 pass
-// 1, 23 rounds (ticks), 24 rounds, 25 chains; Huffman (wave 0): 26 rank, 27 merge, 28
-// lengths, 29 canonical codes, 30 description; 32/33 wave 0's walk ticks / rounds, 34 + w
-// wave w's parse.
-__device__ unsigned long long g_zprobe[64];  // (48..56: the split entropy kernel's phases)
+// of each phase into g_zprobe (slots 4-8, 16 and 18 are no longer written; the numbers are kept:
+// the probe logs under profiles/ were printed from them).
+// zstd_parse_kernel: 0 stage + RLE test, 1 parse, 3 matches out of the literal bitmap +
+// repeat coding + code histograms, 2 literal counts, sampled and full histogram, the item
+// record, 15 literals compacted to global memory, 9 between items (the deal, the barrier,
+// and an item that ended early: empty, RLE or raw); 10 blocks handed to the entropy kernel,
+// 11 their sequences, 12 their literals; 34 + w wave w's parse.  parse_subblock (wave 0):
+// 13 history, 14 rounds + walk; 32/33 the walk's ticks / rounds, 42 after the walk; per
+// round 43 table, 44 candidates, 45 lengths, 46 packed records and chain.
+// zstd_entropy_kernel: 48 the item record loaded, 49 the roles (literal mode beside the
+// sequence tables and chains), 50 Huffman sizes, 51 segment bounds + size decision,
+// 52 sequence header + literal section, 53 sequence bit stream, 54 between items (the deal,
+// the block header or raw block of the item before), 55 blocks; per role (lane 0 of the
+// wave doing it): 17 literal mode (wave 0), 19 LL table (wave 1), 20 LL state chain (wave
+// 1), 21 sizes + literal section (wave 0).  seq_chain_wave (long LL chains): 22 pass 1,
+// 23 rounds (ticks), 24 rounds, 25 chains.  literal_mode_wave: 26 rank, 27 merge,
+// 28 lengths, 29 canonical codes, 30 description.
+__device__ unsigned long long g_zprobe[64];
 // PBS_ZSTD_DEBUG_ITEM=k (diagnostics): the parse's sequences of item k -- per sub-block its
 // count, then its kZSubSeq {pos, ml, off} records -- copied out for a diff with the twin's
 // (zstd_twin_parse)
@@ -1973,603 +1783,19 @@ __device__ uint32_t g_zdbg[kZWaves * (1 + 3 * kZSubSeq)];
         }                                          \
     } while (0)
 
-__global__ __launch_bounds__(kZThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void zstd_block_kernel(
-    const uint8_t* __restrict__ data, uint64_t base, const uint64_t* __restrict__ bounds,
-    const uint64_t* __restrict__ items, uint64_t nitems, uint8_t* __restrict__ slots,
-    uint64_t* __restrict__ sizes, Seq* __restrict__ seq_scratch, Coded* __restrict__ coded_scratch,
-    uint32_t* __restrict__ chain_scratch, int probe_on, int64_t dbg_item) {
-    __shared__ uint4 stage[kZStageWords];
-    __shared__ __attribute__((aligned(16))) uint8_t work[64 * 1024];
-    __shared__ FseT fse[3];  // LL, OF, ML
-    __shared__ FseT fse_huf;  // the Huffman description's scratch (beside the sequence tables)
-    __shared__ PreT pre[3];  // the predefined tables, same order
-    __shared__ Ctl ctl;
-    // (the wave index as a provably uniform value: everything derived from it -- a sub-block's
-    // bounds, the parse's walk state -- then lives in SGPRs and branches on the scalar unit)
-    const int tid = threadIdx.x, lane = tid & 63, wave = (int)uni((uint32_t)tid >> 6);
-    const bool probe = probe_on && blockIdx.x == 0 && tid == 0;
-    uint64_t tp = probe ? wall_clock64() : 0;
-    uint16_t* const tabs = reinterpret_cast<uint16_t*>(work);
-    EntropyArea& E = *reinterpret_cast<EntropyArea*>(work);
-    Seq* const wseq_all = seq_scratch + (uint64_t)blockIdx.x * kZBlockSeq;
-    Coded* const coded = coded_scratch + (uint64_t)blockIdx.x * kZBlockSeq;
-    // per stream, per sequence: the emitted bits, then (as u16) the state before each step,
-    // then (as bytes) the stream's codes in step order
-    uint32_t* const chains = chain_scratch + (uint64_t)blockIdx.x * 6 * kZBlockSeq;
-    if (wave == 0 && lane < 3) {  // the predefined tables, once per launch (fse[] as scratch)
-        FseT& t = fse[lane];
-        if (lane == 0) fse_build(t, kLLNorm, 36, kLLLog);
-        if (lane == 1) fse_build(t, kOFNorm, 29, kOFLog);
-        if (lane == 2) fse_build(t, kMLNorm, 53, kMLLog);
-        PreT& q = pre[lane];
-        for (int i = 0; i < 64; ++i) q.next[i] = t.next[i];
-        for (int i = 0; i < 53; ++i) {
-            q.dnb[i] = t.dnb[i];
-            q.dfs[i] = t.dfs[i];
-        }
-        q.log = t.log;
-    }
-
-    for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
-        __syncthreads();  // LDS of the previous item
-        ZMARK(9);
-        const uint64_t it = items[k];
-        const uint64_t ci = it >> 32, j = (uint32_t)it;
-        const uint64_t c0 = bounds[2 * ci], c1 = bounds[2 * ci + 1];  // (chunk spans {start, end})
-        const uint64_t len = c1 - c0, off = j * (uint64_t)kEncBlock;
-        const uint32_t n = (uint32_t)(len > off ? (len - off < kEncBlock ? len - off : kEncBlock) : 0);
-        const bool last = off + n == len;
-        uint8_t* const out = slots + k * kSlot;
-        if (n == 0) {  // the empty chunk's frame: one empty raw block
-            if (tid == 0) {
-                write_block_header(out, true, 0, 0);
-                sizes[k] = 3;
-            }
-            continue;
-        }
-        const uint32_t hist = (uint32_t)(off < kZHist ? off : kZHist);  // window bytes before the block
-        const uint32_t N = hist + n;
-        // stage the aligned 16-byte words holding [src - hist, src + n)
-        const uint8_t* const wsrc = data + (c0 - base) + off - hist;
-        const uint32_t r = (uint32_t)(reinterpret_cast<uintptr_t>(wsrc) & 15);
-        const uint8_t* const a0 = wsrc - r;
-        const uint32_t nw = (N + r + 15) >> 4;
-        // (with the RLE test: every block byte, LDS bytes [r + hist, r + N), equal to the first)
-        const uint32_t b0 = data[(c0 - base) + off];
-        const uint32_t bb = b0 * 0x01010101u, blo = r + hist, bhi = r + N;
-        auto same_dw = [&](uint32_t a, uint32_t val) {  // the dword at LDS byte a
-            if (a + 4 <= blo || a >= bhi) return true;
-            uint32_t mk = 0xFFFFFFFFu;
-            if (a < blo) mk &= 0xFFFFFFFFu << (8 * (blo - a));
-            if (a + 4 > bhi) mk &= 0xFFFFFFFFu >> (8 * (a + 4 - bhi));
-            return ((val ^ bb) & mk) == 0;
-        };
-        bool same = true;
-        for (uint32_t i0 = tid; i0 < nw; i0 += 4 * kZThreads) {
-            v4u v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t i = i0 + kZThreads * q;
-                if (i < nw) v[q] = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(a0) + i);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t i = i0 + kZThreads * q;
-                if (i < nw) {
-                    stage[i] = make_uint4(v[q].x, v[q].y, v[q].z, v[q].w);
-                    same = same && same_dw(16 * i, v[q].x) && same_dw(16 * i + 4, v[q].y) &&
-                           same_dw(16 * i + 8, v[q].z) && same_dw(16 * i + 12, v[q].w);
-                }
-            }
-        }
-        if (tid < 2) stage[nw + tid] = make_uint4(0, 0, 0, 0);  // word reads past the end stay defined
-        // ---- RLE block: every byte equal
-        if (__syncthreads_and(same)) {
-            ZMARK(0);
-            if (tid == 0) {
-                write_block_header(out, last, 1, n);
-                out[3] = (uint8_t)b0;
-                sizes[k] = 4;
-            }
-            continue;
-        }
-        ZMARK(0);
-        const Win W{(const lds_u32*)stage, r};
-
-        // ---- parse: wave w owns the sub-block [s0, se) (window positions)
-        {
-            const uint64_t tw0 = probe_on && blockIdx.x == 0 ? wall_clock64() : 0;
-            const uint64_t pr = parse_subblock(W, (lds_u16*)tabs, wseq_all, hist, N, wave, lane,
-                                               probe_on && blockIdx.x == 0 && wave == 0 ? g_zprobe : nullptr);
-            const uint32_t ns = (uint32_t)pr, lastend = (uint32_t)(pr >> 32);
-            if (probe_on && blockIdx.x == 0 && lane == 0) atomicAdd(&g_zprobe[34 + wave], wall_clock64() - tw0);
-            if (lane == 0) {
-                ctl.nseq[wave] = ns;
-                ctl.lastend[wave] = lastend;
-            }
-            __threadfence_block();  // the sequence list (global) before the other waves read it (workgroup scope: an agent-scope fence writes back L2)
-        }
-        __syncthreads();
-        ZMARK(1);
-        if ((int64_t)k == dbg_item) {
-            for (uint32_t i = tid; i < kZWaves * (1 + 3 * kZSubSeq); i += kZThreads) {
-                const uint32_t w2 = i / (1 + 3 * kZSubSeq), r2 = i % (1 + 3 * kZSubSeq);
-                g_zdbg[i] = r2 == 0 ? ctl.nseq[w2]
-                                    : reinterpret_cast<const uint32_t*>(wseq_all + (uint64_t)w2 * kZSubSeq)[r2 - 1];
-            }
-        }
-
-        // ---- literals: bitmap of the unmatched bytes, literal index per thread range
-        for (uint32_t i = tid; i < kEncBlock / 32; i += kZThreads) {
-            const uint32_t b = 32 * i;
-            E.bitmap[i] = b + 32 <= n ? 0xFFFFFFFFu : (b >= n ? 0u : (0xFFFFFFFFu >> (32 - (n - b))));
-        }
-        for (uint32_t i = tid; i < kZWaves * 256; i += kZThreads) E.streams[i] = 0;  // per-wave histograms
-        __syncthreads();
-        {
-            // lane per match: its partial end words by atomics, up to 4 whole words by
-            // stores (no other match touches them); longer runs of whole words by the wave
-            const Seq* const wseq = wseq_all + (uint64_t)wave * kZSubSeq;
-            const uint32_t nsw = min(ctl.nseq[wave], kZSubSeq);
-            for (uint32_t q0 = 0; q0 < nsw; q0 += 64) {
-                uint32_t a = 0, b = 0;
-                if (q0 + lane < nsw) {
-                    const Seq e = wseq[q0 + lane];
-                    a = e.pos;
-                    b = e.pos + e.ml;
-                }
-                uint32_t wa = 0, wb = 0;
-                if (a < b) {
-                    if ((a >> 5) == ((b - 1) >> 5)) {
-                        const uint32_t cnt = b - a;
-                        const uint32_t mask = (cnt == 32 ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << (a & 31);
-                        if (cnt == 32)
-                            E.bitmap[a >> 5] = 0;
-                        else
-                            atomicAnd(&E.bitmap[a >> 5], ~mask);
-                    } else {
-                        if (a & 31) atomicAnd(&E.bitmap[a >> 5], (1u << (a & 31)) - 1u);
-                        if (b & 31) atomicAnd(&E.bitmap[b >> 5], ~((1u << (b & 31)) - 1u));
-                        wa = (a + 31) >> 5;
-                        wb = b >> 5;
-                        if (wb - wa <= 4) {
-                            for (uint32_t w = wa; w < wb; ++w) E.bitmap[w] = 0;
-                            wb = wa;
-                        }
-                    }
-                }
-                for (unsigned long long lg = __ballot(wb > wa); lg; lg &= lg - 1) {
-                    const int l = __builtin_ctzll(lg);
-                    const uint32_t la = (uint32_t)__builtin_amdgcn_readlane((int)wa, l);
-                    const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)wb, l);
-                    for (uint32_t w = la + lane; w < lb; w += 64) E.bitmap[w] = 0;
-                }
-            }
-        }
-        __syncthreads();
-        ZMARK(15);
-        // thread t owns block positions [128 t, 128 t + 128): bitmap words 4t .. 4t + 3
-        uint32_t bmw[4], cnt_t = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            bmw[i] = E.bitmap[4 * tid + i];
-            cnt_t += __builtin_popcount(bmw[i]);
-        }
-        // the sampled histogram first: literals at block positions divisible by 16 (one
-        // predicated LDS atomic per 16 positions); the full one only when the sample says
-        // Huffman may pay (random literals never need it)
-        uint32_t* const wh = E.streams + wave * 256;
-        uint32_t samp_t = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if ((bmw[k >> 1] >> ((16 * k) & 31)) & 1u) {
-                atomicAdd(&wh[W.byte(hist + 128 * tid + 16 * k)], 1u);
-                ++samp_t;
-            }
-        }
-        const uint32_t incl = wave_incl(cnt_t, lane);
-        const uint32_t sincl = wave_incl(samp_t, lane);
-        if (lane == 63) {
-            ctl.wsum[wave] = incl;
-            ctl.wsum2[wave] = sincl;
-        }
-        __syncthreads();
-        uint32_t litbase = incl - cnt_t, nlit = 0, nsamp = 0;
-        for (int w2 = 0; w2 < kZWaves; ++w2) {
-            litbase += w2 < wave ? ctl.wsum[w2] : 0u;
-            nlit += ctl.wsum[w2];
-            nsamp += ctl.wsum2[w2];
-        }
-        if (tid < 256) {
-            uint32_t c = 0;
-            for (int w2 = 0; w2 < kZWaves; ++w2) c += E.streams[w2 * 256 + tid];
-            E.hist[tid] = c;
-        }
-        __syncthreads();
-        ZMARK(16);
-        if (wave == 0) {  // 1: the full histogram is needed; 0: raw literals
-            uint32_t need = nlit > 0;
-            if (nlit >= 32 && nsamp > 0) {
-                uint64_t es = 0;
-                const uint32_t lm = lg256(nsamp);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const uint32_t c = E.hist[lane + 64 * i];
-                    if (c) es += (uint64_t)c * (lm - lg256(c));
-                }
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) es += __shfl_xor(es, d, 64);
-                if (es * nlit / nsamp / 2048 + 64 >= (uint64_t)nlit - nlit / 64) need = 0;
-            }
-            if (lane == 0) {
-                ctl.need_full = need;
-                ctl.lit_mode = 0;
-            }
-        }
-        __syncthreads();
-        if (ctl.need_full) {
-            for (uint32_t i = tid; i < kZWaves * 256; i += kZThreads) E.streams[i] = 0;
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                for (uint32_t m2 = bmw[i]; m2; m2 &= m2 - 1)
-                    atomicAdd(&wh[W.byte(hist + 128 * tid + 32 * i + __builtin_ctz(m2))], 1u);
-            __syncthreads();
-            if (tid < 256) {
-                uint32_t c = 0;
-                for (int w2 = 0; w2 < kZWaves; ++w2) c += E.streams[w2 * 256 + tid];
-                E.hist[tid] = c;
-            }
-            __syncthreads();
-        }
-        ZMARK(2);
-
-        // ---- repeat-offset coding (every wave its sub-block), then two independent halves at
-        // once: the literal mode (Huffman code, wave 0) and the sequence side -- per stream (LL
-        // on wave 1, OF on 2, ML on 3) its code histogram, its table and its FSE state chain.
-        // (Round 3 ran them one after the other: the chains waited for the literal mode and the
-        // literal section for the chains -- ~80 us of a ~1.25 ms text block.)
-        const bool role_probe = probe_on && blockIdx.x == 0;
-        uint64_t zt = role_probe ? wall_clock64() : 0;
-        auto role_end = [&](int idx) {
-            if (role_probe && lane == 0) {
-                const uint64_t t2 = wall_clock64();
-                atomicAdd(&g_zprobe[idx], t2 - zt);
-                zt = t2;
-            }
-        };
-        rep_code_wave(ctl.nseq, ctl.lastend, wseq_all, coded, (uint32_t)wave, lane);
-        __threadfence_block();
-        {
-            // this sub-block's code histograms (LL | ML | OF, 121 bins) into the wave's own copy
-            // in the stream buffer (free until the literal section); the stream's wave sums them
-            uint32_t* const wc = E.streams + wave * 128;
-            for (uint32_t i = (uint32_t)lane; i < 128; i += 64) wc[i] = 0;
-            __builtin_amdgcn_wave_barrier();
-            uint32_t first = 0;
-            for (int w2 = 0; w2 < wave; ++w2) first += min(ctl.nseq[w2], kZSubSeq);
-            const uint32_t cnt = min(ctl.nseq[wave], kZSubSeq);
-            for (uint32_t q0 = 0; q0 < cnt; q0 += 64 * 4) {
-                uint32_t cv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t q = q0 + 64 * (uint32_t)u + (uint32_t)lane;
-                    cv[u] = q < cnt ? coded[first + q].codes : 0xFFFFFFFFu;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (cv[u] != 0xFFFFFFFFu) {
-                        atomicAdd(&wc[cv[u] & 0xFF], 1u);
-                        atomicAdd(&wc[36 + ((cv[u] >> 8) & 0xFF)], 1u);
-                        atomicAdd(&wc[36 + 53 + (cv[u] >> 16)], 1u);
-                    }
-            }
-        }
-        if (wave == 1) role_end(18);
-        __syncthreads();
-        ZMARK(3);
-        uint32_t nseq = 0;
-        for (int w2 = 0; w2 < kZWaves; ++w2) nseq += min(ctl.nseq[w2], kZSubSeq);
-        if (wave == 0) {
-            if (ctl.need_full) literal_mode_wave(E, ctl, fse_huf, nlit, lane, role_probe ? g_zprobe : nullptr);
-            role_end(17);
-        } else if (wave <= 3) {
-            const int k = wave - 1;  // 0 LL, 1 OF, 2 ML
-            const uint32_t sh = k == 0 ? 0u : k == 1 ? 16u : 8u;
-            uint32_t* const hk = E.shist + (k == 0 ? 0 : k == 1 ? 36 + 53 : 36);  // (the histogram layout: LL, ML, OF)
-            const uint32_t nbin = k == 0 ? 36u : k == 1 ? 32u : 53u;
-            const uint32_t boff = k == 0 ? 0u : k == 1 ? 36u + 53u : 36u;
-            uint32_t tot = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < kZWaves; ++w2) tot += (uint32_t)lane < nbin ? E.streams[w2 * 128 + boff + lane] : 0u;
-            if ((uint32_t)lane < nbin) hk[lane] = tot;
-            __builtin_amdgcn_wave_barrier();
-            if (nseq > 0) {
-                if (k == 0) seq_table_wave(fse[0], hk, 36, nseq, kLLNorm, kLLLog, kLLMaxLog, lane);
-                if (k == 1) seq_table_wave(fse[1], hk, 29, nseq, kOFNorm, kOFLog, kOFMaxLog, lane);
-                if (k == 2) seq_table_wave(fse[2], hk, 53, nseq, kMLNorm, kMLLog, kMLMaxLog, lane);
-            }
-            if (wave == 1) role_end(19);
-            if (nseq >= 2 && fse[k].mode != 1) {
-                const FseView tv = fse[k].mode == 2 ? view(fse[k]) : view(pre[k]);
-                seq_chain_wave(tv, coded, nseq, sh, chains + (uint64_t)k * kZBlockSeq,
-                               reinterpret_cast<uint16_t*>(chains + 3ull * kZBlockSeq) + (uint64_t)k * kZBlockSeq,
-                               reinterpret_cast<uint8_t*>(chains + 3ull * kZBlockSeq + 3ull * kZBlockSeq / 2) +
-                                   (uint64_t)k * (kZBlockSeq + 16),
-                               &ctl.seq_last[k], lane, role_probe && k == 0 ? g_zprobe : nullptr);
-                __threadfence_block();
-            }
-            if (wave == 1) role_end(20);
-        }
-        __syncthreads();
-        ZMARK(5);
-        // literal runs (few sequences: the raw literals are copied run by run, coalesced)
-        if (wave == 0 && nseq < kZRuns) {
-            const Coded x = (uint32_t)lane < nseq ? coded[lane] : Coded{0, 0, 0, 0};
-            const uint32_t span = x.ll + x.ml, lit = x.ll;
-            const uint32_t si = wave_incl(span, lane), li = wave_incl(lit, lane);
-            if ((uint32_t)lane <= nseq) {
-                ctl.run_start[lane] = si - span;
-                ctl.run_out[lane] = li - lit;
-                ctl.run_len[lane] = (uint32_t)lane < nseq ? lit : (n > si - span ? n - (si - span) : 0u);  // (never a wrapped length)
-            }
-        }
-        // ---- Huffman sizes: per-thread code-length sums, block scan, segment totals
-        const uint32_t lit_mode = ctl.lit_mode;
-        uint32_t bits_t = 0;
-        if (lit_mode == 2) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                for (uint32_t m2 = bmw[i]; m2; m2 &= m2 - 1)
-                    bits_t += E.len[W.byte(hist + 128 * tid + 32 * i + __builtin_ctz(m2))];
-        }
-        const uint32_t bincl = wave_incl(bits_t, lane);
-        if (lane == 63) ctl.wsum2[wave] = bincl;
-        const bool four = nlit >= 256;
-        const uint32_t seg = four ? (nlit + 3) / 4 : nlit;
-        __syncthreads();
-        ZMARK(4);
-        uint32_t bbase = bincl - bits_t;
-        for (int w2 = 0; w2 < wave; ++w2) bbase += ctl.wsum2[w2];
-        if (lit_mode == 2) {
-            // the thread holding literal index seg * s records the bits before it
-            if (tid == 0) {
-                ctl.segP[0] = 0;
-                uint32_t tot = 0;
-                for (int w2 = 0; w2 < kZWaves; ++w2) tot += ctl.wsum2[w2];
-                ctl.segP[4] = tot;
-                if (!four) ctl.segP[1] = tot;
-            }
-            if (four) {
-                uint32_t idx = litbase, pb = bbase;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    for (uint32_t m2 = bmw[i]; m2; m2 &= m2 - 1) {
-                        if (idx == seg || idx == 2 * seg || idx == 3 * seg) ctl.segP[idx / seg] = pb;
-                        pb += E.len[W.byte(hist + 128 * tid + 32 * i + __builtin_ctz(m2))];
-                        ++idx;
-                    }
-            }
-        }
-        __syncthreads();
-        // literal section: size decision (thread 0)
-        if (tid == 0) {
-            uint32_t lm = lit_mode, sz = 0;
-            const uint32_t rawh = nlit < 32 ? 1u : nlit < 4096 ? 2u : 3u;
-            if (lm == 2) {
-                uint32_t sb = 0;
-                const int ns4 = four ? 4 : 1;
-                for (int s = 0; s < ns4; ++s) sb += (ctl.segP[four ? s + 1 : 4] - ctl.segP[s] + 8) / 8;
-                const uint32_t c = ctl.desc_len + (four ? 6u : 0u) + sb;
-                const uint32_t mx = max(nlit, c);
-                const uint32_t hs = mx < 1024 ? 3u : mx < 16384 ? 4u : 5u;
-                if (sb > kHufStreams || hs + c >= rawh + nlit) {
-                    lm = 0;
-                } else {
-                    sz = hs + c;
-                    ctl.huf_c = c;   // the header's compressed size
-                    ctl.huf_hs = hs; // header bytes
-                }
-            }
-            if (lm == 0) sz = rawh + nlit;
-            if (lm == 1) sz = rawh + 1;
-            ctl.lit_mode = lm;
-            ctl.lit_size = sz;
-        }
-        __syncthreads();
-        ZMARK(6);
-        const uint32_t lm = ctl.lit_mode, lsz = ctl.lit_size;
-        uint8_t* const lit_out = out + 3;
-        if (probe) {
-            g_zprobe[10] += 1;
-            g_zprobe[11] += nseq;
-            g_zprobe[12] += nlit;
-        }
-        // ---- the sequence section header (count, modes, table descriptions; thread 0)
-        if (wave == 0 && role_probe) zt = wall_clock64();
-        if (tid == 0) {
-            uint8_t* o = lit_out + lsz;
-            uint8_t* const o0 = o;
-            const uint32_t ns = nseq;
-            if (ns < 128) {
-                *o++ = (uint8_t)ns;
-            } else if (ns < 0x7F00) {
-                *o++ = (uint8_t)((ns >> 8) + 0x80);
-                *o++ = (uint8_t)ns;
-            } else {
-                *o++ = 0xFF;
-                *o++ = (uint8_t)(ns - 0x7F00);
-                *o++ = (uint8_t)((ns - 0x7F00) >> 8);
-            }
-            if (ns) {
-                *o++ = (uint8_t)(fse[0].mode << 6 | fse[1].mode << 4 | fse[2].mode << 2);
-                for (int k = 0; k < 3; ++k)
-                    for (uint32_t i = 0; i < fse[k].desc_len; ++i) *o++ = fse[k].desc[i];
-            }
-            ctl.seq_hdr = (uint32_t)(o - o0);
-            if (ns >= 1)  // a single sequence's states come from its own codes
-                for (int k = 0; k < 3; ++k)
-                    if (fse[k].mode != 1 && ns == 1) {
-                        const uint32_t sh = k == 0 ? 0u : k == 1 ? 16u : 8u;
-                        const FseView tv = fse[k].mode == 2 ? view(fse[k]) : view(pre[k]);
-                        ctl.seq_last[k] = fse_init(tv, (coded[0].codes >> sh) & 0xFF);
-                    }
-        }
-        // ---- the literal section
-        write_literals(E, ctl, W, hist, make_uint4(bmw[0], bmw[1], bmw[2], bmw[3]), litbase, bbase, nlit, lm, four, seg,
-                       lit_out, tid, nseq < kZRuns ? nseq + 1 : 0u);
-        if (wave == 0) role_end(21);
-        // ---- sequences bit stream: per-sequence bit counts, a block scan, then every
-        // thread writes its range of sequences (the last sequence first in the stream) with
-        // atomicOr into the zeroed words
-        __syncthreads();
-        ZMARK(7);
-        {
-            const uint32_t ns = nseq, hdr = ctl.seq_hdr;
-            const uint32_t mode[3] = {fse[0].mode, fse[1].mode, fse[2].mode};
-            const uint32_t per = (ns + kZThreads - 1) / kZThreads;
-            const uint32_t q0 = min(ns, (uint32_t)tid * per), q1 = min(ns, q0 + per);
-            uint32_t st = 0;
-            for (uint32_t q = q0; q < q1; ++q) st += seq_bits(coded[q], q, ns, chains, kZBlockSeq, mode);
-            const uint32_t si = wave_incl(st, lane);
-            if (lane == 63) ctl.wsum[wave] = si;
-            __syncthreads();
-            uint32_t pt = si - st, T = 0;
-            for (int w2 = 0; w2 < kZWaves; ++w2) {
-                pt += w2 < wave ? ctl.wsum[w2] : 0u;
-                T += ctl.wsum[w2];
-            }
-            uint32_t flushb = 0;
-            for (int k = 0; k < 3; ++k)
-                if (ns && mode[k] != 1) flushb += (uint32_t)(mode[k] == 2 ? fse[k].log : pre[k].log);
-            const uint32_t sbytes = ns ? (T + flushb + 1 + 7) / 8 : 0u;
-            const uint32_t body = lsz + hdr + sbytes;
-            const bool ok = body < n;
-            const uint32_t lastw_l = ns ? (8u * (uint32_t)((uintptr_t)(lit_out + lsz + hdr) & 3u) + T + flushb) >> 5 : 0u;
-            if (ok && ns && lastw_l + 1 <= (uint32_t)(sizeof(E.streams) / 4)) {
-                // staged in LDS (the Huffman streams' buffer, free since the literal section was
-                // written), then stored as whole words; word 0 keeps the bytes before S0
-                uint8_t* const S0 = lit_out + lsz + hdr;
-                uint32_t* const A = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(S0) & ~(uintptr_t)3);
-                const uint32_t off0 = 8u * (uint32_t)(S0 - reinterpret_cast<uint8_t*>(A));
-                const uint32_t lastw = lastw_l;
-                uint32_t* const L = E.streams;
-                for (uint32_t wdx = tid; wdx <= lastw; wdx += kZThreads) L[wdx] = 0;
-                __syncthreads();
-                OrBitsL ob;
-                ob.init(L, off0 + (T - pt - st));
-                for (uint32_t q = q1; q-- > q0;) {
-                    const Coded x = coded[q];
-                    const uint32_t llc = x.codes & 0xFF, mlc = (x.codes >> 8) & 0xFF, ofc = x.codes >> 16;
-                    if (q + 1 < ns) {
-                        const uint32_t j = ns - 2 - q;  // (step order)
-                        if (mode[1] != 1) {
-                            const uint32_t c = chains[kZBlockSeq + j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                        if (mode[2] != 1) {
-                            const uint32_t c = chains[2 * kZBlockSeq + j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                        if (mode[0] != 1) {
-                            const uint32_t c = chains[j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                    }
-                    ob.put(x.ll - ll_base(llc), ll_bits(llc));
-                    ob.put(x.ml - ml_base(mlc), ml_bits(mlc));
-                    ob.put(x.ofv - (1u << ofc), ofc);
-                }
-                ob.done();
-                if (tid == kZThreads - 1) {  // the final states (ML, OF, LL) and the end mark
-                    OrBitsL fb;
-                    fb.init(L, off0 + T);
-                    if (mode[2] != 1) fb.put(ctl.seq_last[2], (uint32_t)(mode[2] == 2 ? fse[2].log : pre[2].log));
-                    if (mode[1] != 1) fb.put(ctl.seq_last[1], (uint32_t)(mode[1] == 2 ? fse[1].log : pre[1].log));
-                    if (mode[0] != 1) fb.put(ctl.seq_last[0], (uint32_t)(mode[0] == 2 ? fse[0].log : pre[0].log));
-                    fb.put(1, 1);
-                    fb.done();
-                }
-                __syncthreads();
-                for (uint32_t wdx = tid; wdx <= lastw; wdx += kZThreads)
-                    A[wdx] = wdx ? L[wdx] : (off0 ? A[0] & ((1u << off0) - 1u) : 0u) | L[0];
-            } else if (ok && ns) {
-                uint8_t* const S0 = lit_out + lsz + hdr;
-                uint32_t* const A = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(S0) & ~(uintptr_t)3);
-                const uint32_t off0 = 8u * (uint32_t)(S0 - reinterpret_cast<uint8_t*>(A));
-                const uint32_t lastw = (off0 + T + flushb + 1 - 1) >> 5;
-                if (tid == 0)
-                    for (uint8_t* b = S0; b < reinterpret_cast<uint8_t*>(A + 1); ++b) *b = 0;
-                for (uint32_t wdx = 1 + tid; wdx <= lastw; wdx += kZThreads) A[wdx] = 0;
-                __threadfence_block();  // the zeros (and the section header) stored before any atomicOr
-                __syncthreads();
-                OrBits ob;
-                ob.init(A, off0 + (T - pt - st));
-                for (uint32_t q = q1; q-- > q0;) {
-                    const Coded x = coded[q];
-                    const uint32_t llc = x.codes & 0xFF, mlc = (x.codes >> 8) & 0xFF, ofc = x.codes >> 16;
-                    if (q + 1 < ns) {
-                        const uint32_t j = ns - 2 - q;  // (step order)
-                        if (mode[1] != 1) {
-                            const uint32_t c = chains[kZBlockSeq + j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                        if (mode[2] != 1) {
-                            const uint32_t c = chains[2 * kZBlockSeq + j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                        if (mode[0] != 1) {
-                            const uint32_t c = chains[j];
-                            ob.put(c & 0xFFFF, c >> 16);
-                        }
-                    }
-                    ob.put(x.ll - ll_base(llc), ll_bits(llc));
-                    ob.put(x.ml - ml_base(mlc), ml_bits(mlc));
-                    ob.put(x.ofv - (1u << ofc), ofc);
-                }
-                ob.done();
-                if (tid == kZThreads - 1) {  // the final states (ML, OF, LL) and the end mark
-                    OrBits fb;
-                    fb.init(A, off0 + T);
-                    if (mode[2] != 1) fb.put(ctl.seq_last[2], (uint32_t)(mode[2] == 2 ? fse[2].log : pre[2].log));
-                    if (mode[1] != 1) fb.put(ctl.seq_last[1], (uint32_t)(mode[1] == 2 ? fse[1].log : pre[1].log));
-                    if (mode[0] != 1) fb.put(ctl.seq_last[0], (uint32_t)(mode[0] == 2 ? fse[0].log : pre[0].log));
-                    fb.put(1, 1);
-                    fb.done();
-                }
-            }
-            if (tid == 0) {
-                ctl.seq_ok = ok;
-                ctl.seq_size = body;
-            }
-        }
-        __syncthreads();
-        ZMARK(8);
-        if (!ctl.seq_ok) {  // raw block (dword stores: byte stores cost a 64 KiB block 128 rounds)
-            stage_to_global(out + 3, W, hist, n, (uint32_t)tid, kZThreads);
-            if (tid == 0) {
-                write_block_header(out, last, 0, n);
-                sizes[k] = 3 + (uint64_t)n;
-            }
-        } else if (tid == 0) {
-            write_block_header(out, last, 2, ctl.seq_size);
-            sizes[k] = 3 + (uint64_t)ctl.seq_size;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- split form (round 6)
-// The same blocks in two kernels, byte for byte: zstd_parse_kernel (one 512-thread workgroup
-// per CU: stage, RLE test, parse, then per sub-block the repeat coding and code histograms,
-// the literal bitmap, the literal histogram and the literals compacted to global memory) and
+// ---------------------------------------------------------------- the two kernels
+// A block is encoded by two kernels: zstd_parse_kernel (one 512-thread workgroup per CU:
+// stage, RLE test, parse, then per sub-block the repeat coding and code histograms, the
+// literal bitmap, the literal histogram and the literals compacted to global memory) and
 // zstd_entropy_kernel (256-thread workgroups, three per CU: literal mode on wave 0 beside the
 // LL / OF / ML tables and state chains on waves 1-3, then the literal section and the
-// sequence bit stream from the compacted literals and the coded sequences).  In the fused
-// kernel the entropy half ran on 4 of the block's 8 waves while the others waited at a
-// barrier and no other block could use the CU's LDS; here a CU runs three blocks' entropy
-// halves at once (52 KiB of LDS, 168 VGPRs each) and the parse kernel's waves never wait for one.
-// The batch of items between the two kernels lives in global memory (ZItem, the coded
-// sequences, the literals).
+// sequence bit stream from the compacted literals and the coded sequences).  Two kernels
+// because the entropy half has work for 4 waves only: inside one 8-wave workgroup (the
+// single kernel of rounds up to 5: DESIGN.md section 10) the other waves waited at a
+// barrier and no other block could use the CU's LDS; this way a CU runs three blocks'
+// entropy halves at once (52 KiB of LDS, 168 VGPRs each) and the parse kernel's waves never
+// wait for one.  The batch of items between the two kernels lives in global memory (ZItem,
+// the coded sequences, the literals).
 constexpr int kEThreads = 256;
 constexpr int kEWaves = kEThreads / 64;
 struct ZItem {
@@ -2590,33 +1816,13 @@ struct PArea {
 };
 static_assert(sizeof(PArea) <= 64 * 1024, "the parse kernel's buffers fit the work area");
 struct PCtl {
-    uint32_t nseq[kZWaves], lastend[kZWaves], wsum[kZWaves], wsum2[kZWaves], need_full;
+    uint32_t nseq[kZWaves];     // sequences per sub-block
+    uint32_t lastend[kZWaves];  // end of the sub-block's last match (block position), 0 if none
+    uint32_t wsum[kZWaves], wsum2[kZWaves], need_full;  // block-scan partials; 1: the full literal histogram is needed
     uint32_t run_start[kZRuns], run_len[kZRuns], run_out[kZRuns];  // literal runs of a block with few sequences
 };
-// the entropy kernel's area: the fused kernel's EntropyArea without the literal bitmap (the
-// parse kernel's) and with a 36.5 KiB stream buffer -- Huffman streams up to kHufStreams
-// (48 KiB) longer than it are ORed into the output in global memory instead (same bytes),
-// and so is a sequence bit stream longer than it; with it three workgroups fit a CU's LDS
-constexpr uint32_t kEStreams = 36 * 1024 + 512;  // (3 x the LDS of a workgroup must stay under 160 KiB after the allocation granule)
-struct EArea {
-    // the Huffman merge's scratch (keys, tw, par: literal_mode_wave only) shares the stream
-    // buffer, which is free until the literal section
-    union {
-        uint32_t streams[kEStreams / 4 + 4];
-        struct {
-            uint32_t keys[256];
-            uint32_t tw[512];
-            uint16_t par[512];
-        };
-    };
-    uint32_t hist[256];
-    uint8_t lens[256];
-    uint8_t len[256];
-    uint16_t code[256];
-    uint32_t shist[36 + 53 + 32];
-};
 
-// The split kernels' item dealing.  deal == nullptr: static, item k, k + grid, ... (the
+// The two kernels' item dealing.  deal == nullptr: static, item k, k + grid, ... (the
 // stride passed in); otherwise the next unclaimed item of the launch's counter (zeroed
 // before the launch), so a workgroup that drew cheap items (RLE zero pages, raw blocks the
 // entropy kernel skips) takes more: the VM image's blocks are that uneven.  Every thread
@@ -2712,7 +1918,12 @@ __global__ __launch_bounds__(kZThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         const Win W{(const lds_u32*)stage, r};
         {
             const uint64_t tw0 = probe_on && blockIdx.x == 0 ? wall_clock64() : 0;
-            const uint64_t pr = parse_subblock(W, (lds_u16*)tabs, wseq_all, hist, N, wave, lane,
+            // (the lane as a value the compiler cannot see through: parse_subblock has this one
+            // caller, and with the lane's range known inside it the compiler allocates it
+            // differently -- 252 VGPRs for 250 -- and text ran 0.4 % slower, profiles/zsingle/)
+            int lane_o = lane;
+            asm volatile("" : "+v"(lane_o));
+            const uint64_t pr = parse_subblock(W, (lds_u16*)tabs, wseq_all, hist, N, wave, lane_o,
                                                probe_on && blockIdx.x == 0 && wave == 0 ? g_zprobe : nullptr);
             if (probe_on && blockIdx.x == 0 && lane == 0) atomicAdd(&g_zprobe[34 + wave], wall_clock64() - tw0);
             if (lane == 0) {
@@ -2778,7 +1989,13 @@ __global__ __launch_bounds__(kZThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
                 }
             }
         }
-        rep_code_wave(pc.nseq, pc.lastend, wseq_all, coded, (uint32_t)wave, lane);
+        {
+            // (likewise the two LDS pointers: as constants the compiler unrolls rep_code_wave's
+            // first loop eight times and re-allocates the rest)
+            lds_u32 *nseq_o = (lds_u32*)pc.nseq, *lastend_o = (lds_u32*)pc.lastend;
+            asm volatile("" : "+v"(nseq_o), "+v"(lastend_o));
+            rep_code_wave((const uint32_t*)nseq_o, (const uint32_t*)lastend_o, wseq_all, coded, (uint32_t)wave, lane);
+        }
         __threadfence_block();
         {
             uint32_t* const wc = A.wc + wave * 128;
@@ -2907,8 +2124,8 @@ __global__ __launch_bounds__(kZThreads) __attribute__((amdgpu_waves_per_eu(2, 2)
         for (int w2 = 0; w2 < kZWaves; ++w2) nseq_b += min(pc.nseq[w2], kZSubSeq);
         if (nseq_b < kZRuns) {
             // few sequences (a VM image's random pages: ~40 KB of literals in a handful of
-            // runs): the runs straight from the staged window with dword stores, as the fused
-            // kernel does -- the bitmap compaction below is an LDS byte round trip per literal
+            // runs): the runs straight from the staged window with dword stores -- the bitmap
+            // compaction below is an LDS byte round trip per literal
             if (wave == 0) {
                 const Coded x = (uint32_t)lane < nseq_b ? coded[lane] : Coded{0, 0, 0, 0};
                 const uint32_t span = x.ll + x.ml, lit = x.ll;
@@ -3273,7 +2490,8 @@ __global__ __launch_bounds__(kEThreads) __attribute__((amdgpu_waves_per_eu(3, 3)
         if (wave == 0) role_end(21);
         __syncthreads();
         ZMARK(52);
-        // ---- the sequence bit stream (the fused kernel's, over 256 threads)
+        // ---- the sequence bit stream: thread t's share of the sequences, its bit count, a
+        // block scan for its bit offset, then its bits ORed into the zeroed stream words
         {
             const uint32_t ns = nseq, hdr = ctl.seq_hdr;
             const uint32_t mode[3] = {fse[0].mode, fse[1].mode, fse[2].mode};
@@ -3517,6 +2735,31 @@ extern "C" size_t pbs_blob_stream_bound(const uint64_t* bounds, size_t n) {
     return 12 * n + (size_t)(bounds[n] - bounds[0]);
 }
 
+// PBS_ZSTD_PROBE=1: the launch's g_zprobe slots (see there) as microseconds per block, one
+// line per kernel
+static void print_zprobe(const unsigned long long (&h)[64]) {
+    const double nb = h[10] ? (double)h[10] : 1.0, ne = h[55] ? (double)h[55] : 1.0;
+    const double nc = h[25] ? (double)h[25] : 1.0;
+    auto us = [&](int i, double per) { return h[i] / per / 100; };
+    std::fprintf(stderr,
+                 "zstd probe, parse kernel (workgroup 0, us per block over %llu blocks, %.0f sequences, %.0f literals "
+                 "per block): stage %.1f parse %.1f repcode %.1f litstats %.1f compact %.1f between %.1f | wave 0: "
+                 "history %.1f rounds+walk %.1f | wave 0 walk %.1f in %.1f rounds | parse by wave %.1f %.1f %.1f %.1f "
+                 "%.1f %.1f %.1f %.1f | wave 0 rounds: table %.1f candidates %.1f lengths %.1f pack %.1f records %.1f\n",
+                 h[10], h[11] / nb, h[12] / nb, us(0, nb), us(1, nb), us(3, nb), us(2, nb), us(15, nb), us(9, nb),
+                 us(13, nb), us(14, nb), us(32, nb), h[33] / nb, us(34, nb), us(35, nb), us(36, nb), us(37, nb),
+                 us(38, nb), us(39, nb), us(40, nb), us(41, nb), us(43, nb), us(44, nb), us(45, nb), us(46, nb),
+                 us(42, nb));
+    std::fprintf(stderr,
+                 "zstd probe, entropy kernel (workgroup 0, us per block over %llu blocks): load %.1f roles %.1f "
+                 "sizes %.1f decision %.1f literals %.1f seqstream %.1f between %.1f | roles: litmode %.1f LLtable "
+                 "%.1f LLchain %.1f litsection %.1f | long LL chains %llu: pass 1 %.1f rounds %.1f (%.2f rounds) | "
+                 "Huffman: rank %.1f merge %.1f lengths %.1f codes %.1f describe %.1f\n",
+                 h[55], us(48, ne), us(49, ne), us(50, ne), us(51, ne), us(52, ne), us(53, ne), us(54, ne),
+                 us(17, ne), us(19, ne), us(20, ne), us(21, ne), h[25], us(22, nc), us(23, nc), h[24] / nc,
+                 us(26, ne), us(27, ne), us(28, ne), us(29, ne), us(30, ne));
+}
+
 // The chunks as spans {start, end} (absolute stream offsets; any order, gaps allowed):
 // pbs_blob_encode_spans_device, and pbs_blob_encode_chunks_device through it.  `cfg`: NULL,
 // or the crypt config of the encrypted entry points -- the images are then assembled with
@@ -3603,13 +2846,9 @@ static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base,
     Seq* z_seqs = nullptr;
     Coded* z_coded = nullptr;
     uint32_t* z_chains = nullptr;
-    // the split kernels (default; PBS_ZSTD_SPLIT=0: the fused kernel, A/B): the parse kernel on
-    // one workgroup per CU, the entropy kernel on three per CU, items in batches of zbatch whose
-    // coded sequences, literals and ZItem records wait in global memory between the two
-    static const bool split = [] {
-        const char* e = std::getenv("PBS_ZSTD_SPLIT");
-        return !(e && e[0] == '0');
-    }();
+    // the parse kernel on one workgroup per CU, the entropy kernel on three per CU, items in
+    // batches of zbatch whose coded sequences, literals and ZItem records wait in global memory
+    // between the two
     // (read per call, so a test can run many small batches and both dealings in one process)
     const bool zdeal = [] {  // PBS_ZSTD_DEAL=0: items dealt statically (A/B)
         const char* e = std::getenv("PBS_ZSTD_DEAL");
@@ -3635,20 +2874,14 @@ static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base,
     if (compress) {
         z_slots = ar->get<uint8_t>(kZsSlots, ni * kSlot);
         z_seqs = ar->get<Seq>(kZsSeqs, (size_t)grid * kZBlockSeq * sizeof(Seq));
-        if (split) {
-            z_coded = ar->get<Coded>(kZsCoded, (size_t)bmax * kZBlockSeq * sizeof(Coded));
-            z_chains = ar->get<uint32_t>(kZsChains, (size_t)grid_e * 6 * kZBlockSeq * sizeof(uint32_t));
-            z_items = ar->get<ZItem>(kZsZItems, (size_t)bmax * sizeof(ZItem));
-            z_lits = ar->get<uint8_t>(kZsLits, (size_t)bmax * kEncBlock);
-            if (zdeal && (!(z_deal = ar->get<uint32_t>(kZsDeal, (size_t)nbatch * 4 * sizeof(uint32_t))) ||
-                          !(z_elist = ar->get<uint32_t>(kZsEList, (size_t)bmax * sizeof(uint32_t)))))
-                fail(PBS_ERR_NOMEM);
-            if (!z_items || !z_lits) fail(PBS_ERR_NOMEM);
-        } else {
-            z_coded = ar->get<Coded>(kZsCoded, (size_t)grid * kZBlockSeq * sizeof(Coded));
-            z_chains = ar->get<uint32_t>(kZsChains, (size_t)grid * 6 * kZBlockSeq * sizeof(uint32_t));
-        }
-        if (!z_slots || !z_seqs || !z_coded || !z_chains) fail(PBS_ERR_NOMEM);
+        z_coded = ar->get<Coded>(kZsCoded, (size_t)bmax * kZBlockSeq * sizeof(Coded));
+        z_chains = ar->get<uint32_t>(kZsChains, (size_t)grid_e * 6 * kZBlockSeq * sizeof(uint32_t));
+        z_items = ar->get<ZItem>(kZsZItems, (size_t)bmax * sizeof(ZItem));
+        z_lits = ar->get<uint8_t>(kZsLits, (size_t)bmax * kEncBlock);
+        if (zdeal && (!(z_deal = ar->get<uint32_t>(kZsDeal, (size_t)nbatch * 4 * sizeof(uint32_t))) ||
+                      !(z_elist = ar->get<uint32_t>(kZsEList, (size_t)bmax * sizeof(uint32_t)))))
+            fail(PBS_ERR_NOMEM);
+        if (!z_slots || !z_seqs || !z_coded || !z_chains || !z_items || !z_lits) fail(PBS_ERR_NOMEM);
     }
     if (!d_bounds || !d_items || !d_first || !d_sizes || !d_ipre || !d_bsz || !d_boff || !d_comp || !d_crc || !d_tmp)
         fail(PBS_ERR_NOMEM);
@@ -3677,7 +2910,7 @@ static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base,
             const unsigned long long z[64] = {};
             (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_zprobe), z, sizeof z, 0, hipMemcpyHostToDevice, st);
         }
-        if (compress && split) {
+        if (compress) {
             for (uint64_t b0 = 0; b0 < ni; b0 += bmax) {
                 const uint64_t nb = std::min<uint64_t>(bmax, ni - b0);
                 uint32_t* const dl = z_deal ? z_deal + 4 * (b0 / bmax) : nullptr;
@@ -3690,9 +2923,6 @@ static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base,
                                    z_slots + b0 * kSlot, d_sizes + b0, z_coded, z_lits, z_items, z_chains,
                                    dl ? dl + 1 : nullptr, z_elist, zprobe ? 1 : 0);
             }
-        } else if (compress) {
-            hipLaunchKernelGGL(zstd_block_kernel, dim3(grid), dim3(kZThreads), 0, st, dev_data, base, d_bounds, d_items,
-                               ni, z_slots, d_sizes, z_seqs, z_coded, z_chains, zprobe ? 1 : 0, dbg_item);
         }
         if (compress && dbg_item >= 0) {
             static uint32_t h[kZWaves * (1 + 3 * kZSubSeq)];
@@ -3708,35 +2938,7 @@ static int encode_spans(const uint8_t* dev_data, size_t data_len, uint64_t base,
             unsigned long long h[64] = {};
             (void)hipMemcpyFromSymbolAsync(h, HIP_SYMBOL(g_zprobe), sizeof h, 0, hipMemcpyDeviceToHost, st);
             (void)hipStreamSynchronize(st);
-            const double nb = h[10] ? (double)h[10] : 1.0;
-            std::fprintf(stderr,
-                         "zstd probe (workgroup 0, us per block over %llu blocks, %.0f sequences, %.0f literals per "
-                         "block): stage %.1f parse %.1f litmap %.1f repcode %.1f sizes %.1f litmode||seqside %.1f decision %.1f "
-                         "literals %.1f seqstream %.1f end %.1f | wave 0: history %.1f rounds+walk %.1f | litmap: bitmap %.1f "
-                         "sampled %.1f | roles: litmode %.1f repcode %.1f LLtable %.1f LLchain %.1f litsection %.1f | long LL "
-                         "chains %llu: pass 1 %.1f rounds %.1f (%.2f rounds) | Huffman: rank %.1f merge %.1f lengths %.1f codes "
-                         "%.1f describe %.1f | wave 0 walk %.1f in %.1f rounds | parse by wave %.1f %.1f %.1f %.1f %.1f %.1f %.1f %.1f "
-                         "| wave 0 rounds: table %.1f candidates %.1f lengths %.1f pack %.1f records %.1f\n",
-                         h[10], h[11] / nb, h[12] / nb, h[0] / nb / 100, h[1] / nb / 100, h[2] / nb / 100,
-                         h[3] / nb / 100, h[4] / nb / 100, h[5] / nb / 100, h[6] / nb / 100, h[7] / nb / 100,
-                         h[8] / nb / 100, h[9] / nb / 100, h[13] / nb / 100, h[14] / nb / 100, h[15] / nb / 100,
-                         h[16] / nb / 100, h[17] / nb / 100, h[18] / nb / 100, h[19] / nb / 100, h[20] / nb / 100,
-                         h[21] / nb / 100, h[25], h[25] ? h[22] / (double)h[25] / 100 : 0.0,
-                         h[25] ? h[23] / (double)h[25] / 100 : 0.0, h[25] ? h[24] / (double)h[25] : 0.0,
-                         h[26] / nb / 100, h[27] / nb / 100, h[28] / nb / 100, h[29] / nb / 100, h[30] / nb / 100,
-                         h[32] / nb / 100, h[33] / nb, h[34] / nb / 100, h[35] / nb / 100, h[36] / nb / 100,
-                         h[37] / nb / 100, h[38] / nb / 100, h[39] / nb / 100, h[40] / nb / 100, h[41] / nb / 100,
-                         h[43] / nb / 100, h[44] / nb / 100, h[45] / nb / 100, h[46] / nb / 100, h[42] / nb / 100);
-            if (split) {
-                const double ne = h[55] ? (double)h[55] : 1.0;
-                std::fprintf(stderr,
-                             "zstd probe, entropy kernel (workgroup 0, us per block over %llu blocks): load %.1f roles %.1f "
-                             "sizes %.1f decision %.1f literals %.1f seqstream %.1f end %.1f | roles: litmode %.1f LLtable "
-                             "%.1f LLchain %.1f litsection %.1f\n",
-                             h[55], h[48] / ne / 100, h[49] / ne / 100, h[50] / ne / 100, h[51] / ne / 100,
-                             h[52] / ne / 100, h[53] / ne / 100, h[54] / ne / 100, h[17] / ne / 100, h[19] / ne / 100,
-                             h[20] / ne / 100, h[21] / ne / 100);
-            }
+            print_zprobe(h);
         }
         hipLaunchKernelGGL(zstd_frame_sizes_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st,
                            d_bounds, d_first, d_sizes, (uint64_t)n, compress, d_bsz, d_comp, hdr);

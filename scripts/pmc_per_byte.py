@@ -4,7 +4,7 @@ or bench JSON line gives the bytes per dispatch).  Prints a JSON record per (bui
 workload): counters per dispatch and per input byte, wave-cycle shares and the clock
 (GRBM_GUI_ACTIVE / 8 XCDs / kernel ms when a duration is given).
 
-    python scripts/pmc_per_byte.py gpurun_out/pmc_zstd --kernel zstd_block_kernel
+    python scripts/pmc_per_byte.py profiles/out/pmc_zstd --kernel zstd_parse_kernel
     python scripts/pmc_per_byte.py gpurun_out/pmc_scan --kernel scan_fused_kernel --bytes 68719476736
 """
 import argparse

@@ -1,9 +1,10 @@
 """Same-box A/B of the GPU blob stage on the zstd corpora: one process per library (the
 library under test through PBS_LIBPBSCHUNK_AB, else the in-tree build), best of --reps
-encodes of --gib GiB per corpus, one JSON line per corpus.  Used with scripts/gpu_runs/zstd_ab.sh,
+encodes of --gib GiB per corpus (text, pxar: the seeded 32 MiB corpora tiled; vm: the bench's
+VM-image stream from the device generator), one JSON line per corpus.  Used with scripts/gpu_runs/zstd_ab.sh,
 which alternates the libraries.
 
-    python scripts/zstd_ab.py [--corpus text,pxar] [--gib 1] [--reps 5]
+    python scripts/zstd_ab.py [--corpus text,pxar,vm] [--gib 1] [--reps 5]
 """
 import argparse
 import json
@@ -30,9 +31,15 @@ def main():
 
     torch.cuda.set_device(0)
     for name in a.corpus.split(","):
-        base = {"text": lambda: corpus_gen.text(32 << 20, 21), "pxar": lambda: corpus_gen.pxar(32 << 20, 22)}[name]()
-        n = int(a.gib * (1 << 30)) // base.size * base.size
-        dev = torch.from_numpy(np.tile(base, n // base.size)).to("cuda")
+        if name == "vm":  # the bench's VM-image stream (bench.py SEEDS), generated on the device
+            n = int(a.gib * (1 << 30))
+            dev = torch.empty(n, dtype=torch.uint8, device="cuda")
+            pbschunk.generate_device(dev.data_ptr(), n, pbschunk.GEN_VMIMAGE, 0x5EED0003)
+            torch.cuda.synchronize()
+        else:
+            base = {"text": lambda: corpus_gen.text(32 << 20, 21), "pxar": lambda: corpus_gen.pxar(32 << 20, 22)}[name]()
+            n = int(a.gib * (1 << 30)) // base.size * base.size
+            dev = torch.from_numpy(np.tile(base, n // base.size)).to("cuda")
         with pbschunk.Chunker(a.avg) as c:
             ends = c.find_cuts_device(dev.data_ptr(), n, is_final=True)
         bounds = np.concatenate([[0], ends]).astype(np.uint64)

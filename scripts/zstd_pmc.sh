@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (one counter group per rocprofv3 run, kernel trace only) over the zstd kernels
-# (round 6: zstd_parse_kernel and zstd_entropy_kernel; PBS_ZSTD_SPLIT=0: zstd_block_kernel):
+# (zstd_parse_kernel and zstd_entropy_kernel):
 # the current build and, with BUILDS="cur r04", round 4's through PBS_LIBPBSCHUNK_AB.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp

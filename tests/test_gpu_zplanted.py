@@ -2,8 +2,8 @@
 tests/zplanted.py: matches on the sub-block seams, the window edge and the block and chunk
 ends, match extension and repeat codes at their edges, sequence counts and literal sizes at
 every header and kernel threshold, the frame one byte either side of the chunk's length,
-every start residue mod 16 -- through the split kernels (default), small batches dealt
-statically, the spans entry point and, in a child process, the fused kernel.
+every start residue mod 16 -- through the chunks entry point, small batches dealt statically
+and the spans entry point.
 
 Every blob must equal oracle.blob_compressed(chunk) -- the host twin's frame -- byte for
 byte, carry zlib's CRC and the right compressed flag, and decode with libzstd back to the
@@ -12,11 +12,7 @@ for.
 
 Run on an MI355X:  python -m pytest tests/test_gpu_zplanted.py -m gpu -x -q
 """
-import os
-import pickle
 import struct
-import subprocess
-import sys
 import zlib
 
 import numpy as np
@@ -25,11 +21,6 @@ import pytest
 import zplanted as z
 
 pytestmark = pytest.mark.gpu
-
-# The split kernels' in-process calls over all families take 0.6 s together on an MI355X and
-# the fused-kernel child 2.5 s (most of it starting Python and torch and building the cases);
-# a cold start of torch can take ten seconds more, so a minute before the child counts as hung.
-FUSED_CHILD_TIMEOUT = 60
 
 
 @pytest.fixture(scope="module")
@@ -91,26 +82,3 @@ def test_family_in_small_static_batches(gpu, oracle, torch_dev, monkeypatch, fam
     monkeypatch.setenv("PBS_ZSTD_DEAL", "0")
     labels, chunks, result = z.gpu_encode_family(gpu, torch_dev, family)
     _check(oracle, labels, chunks, result)
-
-
-def test_all_families_fused_kernel(gpu, oracle, tmp_path):
-    """zstd_block_kernel (PBS_ZSTD_SPLIT=0, read once per process): one fresh child process
-    encodes every family and writes the blobs to a file; the same checks on them here."""
-    out = tmp_path / "fused.pkl"
-    env = dict(os.environ, PBS_ZSTD_SPLIT="0")
-    env.pop("PBS_ZSTD_BATCH", None)
-    env.pop("PBS_ZSTD_DEAL", None)
-    r = subprocess.run([sys.executable, os.path.abspath(z.__file__), "encode", str(out)], env=env,
-                       capture_output=True, text=True, timeout=FUSED_CHILD_TIMEOUT)
-    assert r.returncode == 0, f"exit status {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    with open(out, "rb") as f:
-        res = pickle.load(f)
-    assert sorted(res) == sorted(z.FAMILIES)
-    for family in sorted(z.FAMILIES):
-        cs = z.cases(family)
-        if family == "j":
-            _, spans, residues = z.layout_spans(cs[0].chunk)
-            labels, chunks = z.span_labels(cs[0].label, residues), [cs[0].chunk] * len(spans)
-        else:
-            labels, chunks = [c.label for c in cs], [c.chunk for c in cs]
-        _check(oracle, [f"fused {lab}" for lab in labels], chunks, res[family])

@@ -3,8 +3,8 @@
 
 The encoder (proxmox-backup_amd/csrc/pbs_zstd.hip) parses a 64 KiB block as eight
 sub-blocks, one wave and one hash table each, and its entropy stage changes path at a
-handful of sizes.  The geometry below restates those values once, each with its source
-line; test_zplanted_cpu.py pins the seam table and the window to the host twin's behaviour
+handful of sizes.  The geometry below restates those values once, each with the symbol
+it restates; test_zplanted_cpu.py pins the seam table and the window to the host twin's behaviour
 (oracle/zstd_twin.cpp), so a change of either fails there first.
 
 Every case is (label, chunk, predicate).  The predicate is evaluated on the CPU against the
@@ -36,25 +36,25 @@ import numpy as np
 
 KiB = 1024
 # ---- geometry (pbs_zstd.hip unless stated) -------------------------------------------
-BLOCK = 64 * KiB                  # zstd_enc.h:27 kEncBlock
-ZSUB_DELTA = 768                  # :76 PBS_ZSUB_DELTA
-ZSUB_A, ZSUB_B = 8192 + ZSUB_DELTA, 8192 - ZSUB_DELTA  # :78 kZSubA / kZSubB
+BLOCK = 64 * KiB                  # zstd_enc.h kEncBlock
+ZSUB_DELTA = 768                  # PBS_ZSUB_DELTA
+ZSUB_A, ZSUB_B = 8192 + ZSUB_DELTA, 8192 - ZSUB_DELTA  # kZSubA / kZSubB
 
 
-def sub_start(w: int) -> int:     # :79 zsub_start
+def sub_start(w: int) -> int:     # zsub_start
     return w * ZSUB_A if w <= 4 else 4 * ZSUB_A + (w - 4) * ZSUB_B
 
 
 SEAMS = tuple(sub_start(w) for w in range(1, 8))  # 8960 17920 26880 35840 43264 50688 58112
-ZHIST = 16384                     # :82 kZHist: bytes of the previous block staged
-ZROUND, ZCAP, ZMIN, ZMAXSTEP, ZBACK = 256, 32, 5, 8, 8  # :83
-ZWIN = 12288                      # :93 PBS_ZWIN -> :96 kZWin
-ZSUBSEQ = ZSUB_A // ZMIN + 2      # :101 kZSubSeq
-HUFSTREAMS = 48 * KiB             # :108 kHufStreams
-HUFMAX = 11                       # :109 kHufMax
-ZRUNS = 64                        # :110 kZRuns
-ESTREAMS = 36 * KiB + 512         # :2600 kEStreams
-ZEXT_LANE, ZEXT_STEP = 16, 1024   # :1459 / :1478 capped match: 16 bytes per lane, 64 lanes a step
+ZHIST = 16384                     # kZHist: bytes of the previous block staged
+ZROUND, ZCAP, ZMIN, ZMAXSTEP, ZBACK = 256, 32, 5, 8, 8  # kZRound, kZCap, kZMin, kZMaxStep, kZBack
+ZWIN = 12288                      # PBS_ZWIN -> kZWin
+ZSUBSEQ = ZSUB_A // ZMIN + 2      # kZSubSeq
+HUFSTREAMS = 48 * KiB             # kHufStreams
+HUFMAX = 11                       # kHufMax
+ZRUNS = 64                        # kZRuns
+ESTREAMS = 36 * KiB + 512         # kEStreams
+ZEXT_LANE, ZEXT_STEP = 16, 1024   # parse_subblock's capped match: 16 bytes per lane, 64 lanes a step
 # header-size thresholds (RFC 8878; the writers in zstd_twin.cpp)
 FCS_EDGES = (256, 65536 + 256)    # frame content size in 1 / 2 / 4 bytes (frame_header)
 SEQ_COUNT_EDGE = 128              # sequence count in 1 / 2 bytes (sequences)
@@ -370,7 +370,7 @@ _OFFS8 = tuple(range(4096, 4096 + 8 * 24, 8))
 
 
 def hash5(b) -> int:
-    """The table hash of 5 bytes (pbs_zstd.hip:155, zstd_twin.cpp hash5)."""
+    """The table hash of 5 bytes (pbs_zstd.hip hash5, zstd_twin.cpp hash5)."""
     w = int.from_bytes(bytes(b[:4]), "little")
     return ((((w * 2654435761) & 0xFFFFFFFF) ^ ((int(b[4]) * 2246822519) & 0xFFFFFFFF)) >> 20) & 0xFFF
 
@@ -390,7 +390,7 @@ def _shadow(buf: np.ndarray, at: int, victim: int, seed: int) -> None:
 
 def extension_recipes():
     """c. Match lengths around kZMin, kZCap and the capped match's forward extension (16
-    bytes per lane, 1024 bytes a step, pbs_zstd.hip:1458-1479; 256 past the cap as well);
+    bytes per lane, 1024 bytes a step, the walk of pbs_zstd.hip parse_subblock; 256 past the cap as well);
     matches that run to the sub-block, block and chunk end; backward extension of 0, 1, 7, 8
     and 9 bytes before a sampled hit (capped at kZBack; the position 8 bytes earlier is kept
     out of the table by a later position with the same hash), and one stopped by the
@@ -840,7 +840,7 @@ def case(label: str) -> Case:
     return _case(recipes(label[0])[label])
 
 
-# ---- the GPU side (test_gpu_zplanted.py and its fused-kernel child) ------------------
+# ---- the GPU side (test_gpu_zplanted.py) ---------------------------------------------
 
 PAD, GUARD = 5, 4096
 RESIDUES = tuple(range(16))
@@ -1027,17 +1027,3 @@ if __name__ == "__main__":
         for k, val in FOUND.items():
             print(f"    {k!r}: {val!r},")
         print("}")
-    elif sys.argv[1:2] == ["encode"]:  # the fused-kernel child of test_gpu_zplanted.py: every family's blobs
-        import pickle
-        import time
-
-        import pbschunk as _g
-        import torch as _t
-        _t.cuda.set_device(0)
-        res = {}
-        for fam in sorted(FAMILIES):
-            t0 = time.perf_counter()
-            res[fam] = gpu_encode_family(_g, _t, fam)[2]
-            print(f"family {fam}: {time.perf_counter() - t0:.3f} s", flush=True)
-        with open(sys.argv[2], "wb") as f:
-            pickle.dump(res, f)

@@ -150,6 +150,90 @@ int pbs_blob_encode_spans_encrypted_device(const uint8_t *dev_data, size_t data_
 /* 44 n + (bounds[n] - bounds[0]): the largest encrypted blob stream of n chunks. */
 size_t pbs_blob_stream_bound_encrypted(const uint64_t *bounds, size_t n);
 
+/* ---- Reading blobs: DataBlob::load_from_reader (from_raw + verify_crc, data_blob.rs:256-300,
+ * :78-84), DataBlob::decode (:197-253), DataBlob::verify_unencrypted (:310-333) and
+ * CryptConfig::decode_uncompressed_chunk / decode_compressed_chunk (:409-480) -- everything
+ * but the zstd inflate.
+ *
+ * Blob i is [blob_offsets[i], blob_offsets[i+1]) of `blobs_dev` (device; offsets on the host,
+ * n + 1 ascending values at any alignment, n < 2^32); the four kinds may be mixed freely and
+ * the input is never written.  The payloads are written back to back into `out_dev`
+ * (device): payload i is [out_offsets[i], out_offsets[i+1]) (host, n + 1) -- the chunk bytes
+ * for kinds 0 and 2, the zstd frame (decrypted for kind 3) for kinds 1 and 3.  A blob that
+ * fails before its payload length is known (TOO_SMALL, BAD_MAGIC) has a zero-length payload.
+ * `kinds[i]`: PBS_BLOB_KIND_*, or PBS_BLOB_KIND_NONE where the magic is absent or unknown.
+ *
+ * `status[i]` is the first check that fails, in the reference's order (PBS_BLOB_ST_*); a bad
+ * blob never fails the call -- it returns PBS_OK -- and never changes another blob's output.
+ * `cfg` may be NULL: encrypted blobs then get NO_CONFIG (after their CRC check, as load
+ * comes before decode).  `expect_digests` (NULL or 32 n host bytes) is checked for kinds 0
+ * and 2 only -- SHA-256(payload), for kind 2 SHA-256(payload || id_key) -- and `expect_sizes`
+ * (NULL or n host values) for kind 0 only (verify_unencrypted returns Ok for encrypted blobs).
+ * FOR KINDS 1 AND 3 THE DIGEST AND THE SIZE BELONG TO THE INFLATED DATA: the call stops at
+ * OK after CRC and tag, and the caller inflates the frame it gets and checks the digest with
+ * the digest calls of pbs_digest.h.
+ *
+ * No unauthenticated plaintext is released: the output bytes of every encrypted blob whose
+ * status is not OK are zero when the call returns.  (An unencrypted blob that fails keeps
+ * its payload bytes in the output; its status says what is wrong with them.)  No key byte
+ * appears in any error text.
+ *
+ * `out_cap` below pbs_blob_decode_bound: PBS_ERR_CAPACITY before anything is written.
+ * Device scratch comes from a work area kept between calls until pbs_blob_encode_release.
+ * All launches go on `hip_stream`; synchronous. */
+#define PBS_BLOB_KIND_UNCOMPRESSED 0
+#define PBS_BLOB_KIND_COMPRESSED 1
+#define PBS_BLOB_KIND_ENCRYPTED 2
+#define PBS_BLOB_KIND_ENCR_COMPR 3
+#define PBS_BLOB_KIND_NONE 255
+
+#define PBS_BLOB_ST_OK 0
+#define PBS_BLOB_ST_TOO_SMALL 1  /* under 12 bytes, or an encrypted magic under 44 (from_raw :269-281) */
+#define PBS_BLOB_ST_BAD_MAGIC 2  /* :287-289 */
+#define PBS_BLOB_ST_BAD_CRC 3    /* stored CRC != CRC-32 of everything after the header (verify_crc) */
+#define PBS_BLOB_ST_NO_CONFIG 4  /* encrypted kind and cfg == NULL (:247-249) */
+#define PBS_BLOB_ST_BAD_TAG 5    /* GCM tag over the ciphertext != header tag (decrypt_aead) */
+#define PBS_BLOB_ST_BAD_DIGEST 6 /* kinds 0 and 2 (verify_digest :335-349) */
+#define PBS_BLOB_ST_BAD_SIZE 7   /* kind 0 (:324-331) */
+
+#define PBS_ERR_TAG (-7) /* pbs_aes256gcm_decrypt_host: the tag does not match; `out` is zeroed */
+
+typedef struct {
+    double total_ms;    /* call entry .. outputs on the host */
+    double classify_ms; /* size / magic checks, payload lengths, offset scan (HIP events) */
+    double crc_ms;      /* payload CRCs */
+    double decrypt_ms;  /* J0 setup, GHASH + CTR out of place, tag comparison; the copies of the
+                           unencrypted payloads */
+    double digest_ms;   /* SHA-256 lanes, verdicts, wipe of failed encrypted payloads */
+    uint64_t bytes_in, bytes_out;
+    uint64_t gcm_segments; /* PBS_GCM_SEGMENT_BYTES pieces opened */
+    uint64_t failed;       /* blobs whose status is not OK */
+} pbs_blob_decode_timing;
+
+int pbs_blob_decode_device(const uint8_t *blobs_dev, const uint64_t *blob_offsets, size_t n,
+                           const pbs_crypt_config *cfg, const uint8_t *expect_digests,
+                           const uint64_t *expect_sizes, uint8_t *out_dev, size_t out_cap,
+                           uint64_t *out_offsets, uint8_t *kinds, uint8_t *status,
+                           pbs_blob_decode_timing *timing, void *hip_stream);
+/* The most payload bytes n blobs at these offsets can hold: every blob's length less the
+ * 12-byte header -- (blob_offsets[n] - blob_offsets[0]) - 12 n when no blob is shorter than
+ * a header (a shorter one counts as empty). */
+size_t pbs_blob_decode_bound(const uint64_t *blob_offsets, size_t n);
+
+/* Opens what pbs_aes256gcm_encrypt_host seals: the tag over `data` (len ciphertext bytes) is
+ * computed and compared first; PBS_OK and the plaintext in `out` (may alias `data`), or
+ * PBS_ERR_TAG and `out` zeroed. */
+int pbs_aes256gcm_decrypt_host(const pbs_crypt_config *cfg, const uint8_t iv[16], const uint8_t *data,
+                               size_t len, const uint8_t tag[16], uint8_t *out);
+
+/* pbs_blob_decode_device for one blob on the host, with the same kinds and status codes (for
+ * small blobs and tests; not a fast path).  `expect_digest`: NULL or 32 bytes; `expect_size`:
+ * NULL or one value.  The payload goes to `out` (cap >= len - header, else PBS_ERR_CAPACITY)
+ * and its length to *out_len; a failed encrypted blob leaves zeros there. */
+int pbs_blob_decode_host(const uint8_t *blob, size_t len, const pbs_crypt_config *cfg,
+                         const uint8_t *expect_digest, const uint64_t *expect_size, uint8_t *out,
+                         size_t cap, size_t *out_len, uint8_t *kind, uint8_t *status);
+
 #ifdef __cplusplus
 }
 #endif

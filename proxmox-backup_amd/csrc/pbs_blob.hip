@@ -365,6 +365,31 @@ hipError_t pbs::launch_crc32_skip(const uint8_t* data, const uint64_t* bounds_de
     return hipGetLastError();
 }
 
+// The per-blob skip form (pbs_decode.hip: 12 or 44 header bytes, blob by blob): payload i is
+// [spans_dev[2 i], spans_dev[2 i + 1]) of `data`, order_dev[k] = 2 k, and the CRC of payload i
+// lands in out[2 i] (out: 2 n entries).  The same kernel as above -- a span is a "chunk"
+// whose bounds pair is its own, reached through the order list -- with the dynamic order.
+hipError_t pbs::launch_crc32_spans(const uint8_t* data, const uint64_t* spans_dev, const uint32_t* order_dev,
+                                   uint64_t n, uint32_t* out, hipStream_t st) {
+    int dev = 0, ncu = 0;
+    if (hipStreamGetDevice(st, &dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return hipErrorInvalidDevice;
+    const CrcTables* tab = device_tables(dev);
+    if (!tab) return hipErrorOutOfMemory;
+    const unsigned grid = (unsigned)std::min<uint64_t>(n, (uint64_t)ncu * kCrcGroupsPerCu);
+    unsigned long long* ctr = nullptr;
+    if (n > grid) {
+        ctr = stream_counter(st, dev);
+        if (!ctr) return hipErrorOutOfMemory;
+        const hipError_t e = hipMemsetAsync(ctr, 0, sizeof(unsigned long long), st);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(crc32_chunks_kernel, dim3(grid), dim3(kCrcThreads), 0, st, data, (uint64_t)0, spans_dev,
+                       order_dev, n, tab, out, ctr, (uint64_t)0);
+    return hipGetLastError();
+}
+
 extern "C" int pbs_crc32_chunks_async(const uint8_t* dev_data, size_t data_len, uint64_t base,
                                       const uint64_t* bounds_dev, const uint32_t* order_dev, size_t n,
                                       uint32_t* crcs_dev, void* hip_stream) {

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "buzhash_table.h"
+#include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 
@@ -1598,6 +1599,7 @@ const char* pbs_strerror(int code) {
         case PBS_ERR_NOMEM: return "out of memory";
         case PBS_ERR_CAPACITY: return "output array too small";
         case PBS_ERR_INVALID: return "invalid argument";
+        case PBS_ERR_TAG: return "AES-GCM tag mismatch";
         default: return "unknown error";
     }
 }

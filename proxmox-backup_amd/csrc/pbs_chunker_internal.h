@@ -144,6 +144,12 @@ hipError_t exclusive_sum_u64(void* tmp, size_t* tmp_bytes, const uint64_t* in, u
 // pbs_blob.hip: CRC-32 of blob payloads [bounds[i] + skip, bounds[i+1]) of `data`
 hipError_t launch_crc32_skip(const uint8_t* data, const uint64_t* bounds_dev, uint64_t n, uint64_t skip,
                              uint32_t* out, hipStream_t st);
+// pbs_blob.hip: CRC-32 of the spans [spans_dev[2 i], spans_dev[2 i + 1]) of `data` into out[2 i],
+// with order_dev[k] = 2 k (the per-blob header skip of pbs_decode.hip)
+hipError_t launch_crc32_spans(const uint8_t* data, const uint64_t* spans_dev, const uint32_t* order_dev,
+                              uint64_t n, uint32_t* out, hipStream_t st);
+// pbs_decode.hip: frees the idle work areas of pbs_blob_decode_device (pbs_blob_encode_release)
+void decode_release();
 // pbs_crypt.hip: AES-256-GCM in place over the payloads of n blob images (plaintext at
 // blob + 44; blob i = [boff[i], boff[i+1]), offsets on host and device), IV and tag into the
 // headers; asynchronous on `st`.  Takes 5 arena slots from `slot0`; `hs` holds the host

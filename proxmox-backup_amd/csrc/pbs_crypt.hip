@@ -42,10 +42,13 @@
 
 #include "aes_gcm.h"
 #include "dev_arena.h"
+#include "gcm_dev.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 #include "pbs_digest.h"
+
+using pbs::gcm::B128;
 
 namespace pbs {
 namespace gcm {
@@ -54,36 +57,10 @@ constexpr int kThreads = 256;
 constexpr int kRows = PBS_GCM_SEGMENT_BYTES / 16 / kThreads;  // 16 blocks per lane and segment
 constexpr uint32_t kSegBlocks = PBS_GCM_SEGMENT_BYTES / 16;
 constexpr int kGroupsPerCu = 3;  // 40 KiB of LDS and 160 VGPRs each: three fit a CU
+static_assert(kThreads == kGcmThreads && kRows == kGcmRows && kSegBlocks == kGcmSegBlocks &&
+                  kGroupsPerCu == kGcmGroupsPerCu,
+              "the sealing kernel's geometry is the one gcm_dev.h shares with pbs_decode.hip");
 
-// what the kernels read of a key, one copy per device
-struct KeyDev {
-    uint32_t rk[60];
-    uint32_t pad[4];
-    uint32_t te0[256];
-    uint8_t tab_g[32 * 16 * 16];  // [nibble position][value]: (value at position) * H^256, as bytes
-    B128 lane_pow[kThreads];      // H^(256 - t)
-    B128 h, h_seg;                // H, H^4096
-};
-
-struct BlobCtx {
-    uint4 j0;  // big-endian columns
-    B128 ek;   // AES_K(J0)
-};
-
-}  // namespace gcm
-}  // namespace pbs
-
-using pbs::gcm::B128;
-
-struct pbs_crypt_config {
-    uint8_t id_key[32];
-    pbs::gcm::KeyDev key;
-    std::mutex mu;
-    std::map<int, pbs::gcm::KeyDev*> dev;
-};
-
-namespace pbs {
-namespace gcm {
 namespace {
 
 void wipe(void* p, size_t n) {
@@ -144,56 +121,6 @@ void make_key(const uint8_t enc_key[32], KeyDev& k) {
         for (uint32_t v = 0; v < 16; ++v) store_block(k.tab_g + (pos * 16 + v) * 16, gf_mul(nibble_elem(pos, v), g));
 }
 
-KeyDev* device_key(const pbs_crypt_config* cc, int dev) {
-    pbs_crypt_config* c = const_cast<pbs_crypt_config*>(cc);
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = c->dev.find(dev);
-    if (it != c->dev.end()) return it->second;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return nullptr;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
-    KeyDev* d = nullptr;
-    bool ok = hipMalloc(&d, sizeof(KeyDev)) == hipSuccess;
-    // on a private non-blocking stream, as the CRC tables (pbs_blob.hip)
-    hipStream_t cs = nullptr;
-    if (ok && (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess ||
-               hipMemcpyAsync(d, &c->key, sizeof(KeyDev), hipMemcpyHostToDevice, cs) != hipSuccess ||
-               hipStreamSynchronize(cs) != hipSuccess)) {
-        (void)hipFree(d);
-        ok = false;
-    }
-    if (cs) (void)hipStreamDestroy(cs);
-    if (cur != dev) (void)hipSetDevice(cur);
-    if (!ok) return nullptr;
-    c->dev[dev] = d;
-    return d;
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_u __attribute__((aligned(1)));
-
-__host__ __device__ __forceinline__ B128 words_to_b128(uint4 w) {
-    return B128{(uint64_t)__builtin_bswap32(w.x) << 32 | __builtin_bswap32(w.y),
-                (uint64_t)__builtin_bswap32(w.z) << 32 | __builtin_bswap32(w.w)};
-}
-
-// x * H^256 with x and the result as the block's four little-endian memory words
-__host__ __device__ __forceinline__ uint4 mul_tab(const uint4* tg, uint4 x) {
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    uint4 r = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const uint32_t b = (w[i >> 2] >> (8 * (i & 3))) & 255u;
-        const uint4 a = tg[(2 * i) * 16 + (b >> 4)];
-        const uint4 c = tg[(2 * i + 1) * 16 + (b & 15u)];
-        r.x ^= a.x ^ c.x;
-        r.y ^= a.y ^ c.y;
-        r.z ^= a.z ^ c.z;
-        r.w ^= a.w ^ c.w;
-    }
-    return r;
-}
-
 __global__ void gcm_prepare_kernel(const KeyDev* __restrict__ key, const uint8_t* __restrict__ ivs,
                                    const uint64_t* __restrict__ boff, uint64_t n, uint8_t* __restrict__ blobs,
                                    BlobCtx* __restrict__ ctx) {
@@ -208,11 +135,6 @@ __global__ void gcm_prepare_kernel(const KeyDev* __restrict__ key, const uint8_t
     aes256_encrypt(key->rk, Te0Array{key->te0}, s);
     ctx[i].ek = B128{(uint64_t)s[0] << 32 | s[1], (uint64_t)s[2] << 32 | s[3]};
 }
-
-struct Te0Lds {
-    const uint32_t* t;  // te + (lane & 31)
-    __device__ __forceinline__ uint32_t operator()(uint32_t x) const { return t[x << 5]; }
-};
 
 __global__ __launch_bounds__(kThreads) void gcm_ctr_ghash_kernel(
     const KeyDev* __restrict__ key, const uint64_t* __restrict__ items, uint64_t nitems,
@@ -321,6 +243,32 @@ __global__ void gcm_tag_kernel(const KeyDev* __restrict__ key, const uint64_t* _
 }
 
 }  // namespace
+
+KeyDev* device_key(const pbs_crypt_config* cc, int dev) {
+    pbs_crypt_config* c = const_cast<pbs_crypt_config*>(cc);
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = c->dev.find(dev);
+    if (it != c->dev.end()) return it->second;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return nullptr;
+    if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
+    KeyDev* d = nullptr;
+    bool ok = hipMalloc(&d, sizeof(KeyDev)) == hipSuccess;
+    // on a private non-blocking stream, as the CRC tables (pbs_blob.hip)
+    hipStream_t cs = nullptr;
+    if (ok && (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess ||
+               hipMemcpyAsync(d, &c->key, sizeof(KeyDev), hipMemcpyHostToDevice, cs) != hipSuccess ||
+               hipStreamSynchronize(cs) != hipSuccess)) {
+        (void)hipFree(d);
+        ok = false;
+    }
+    if (cs) (void)hipStreamDestroy(cs);
+    if (cur != dev) (void)hipSetDevice(cur);
+    if (!ok) return nullptr;
+    c->dev[dev] = d;
+    return d;
+}
+
 }  // namespace gcm
 
 // Encrypts the payloads of n blob images in place (blob i = [boff[i], boff[i+1]) of

@@ -2727,6 +2727,7 @@ extern "C" size_t pbs_zstd_frame_bound(size_t len) { return (size_t)zstd::frame_
 // and the calling thread's CRC counters of the shared streams.
 extern "C" void pbs_blob_encode_release(void) {
     zpool().clear();
+    decode_release();
     release_thread_counters();
 }
 

@@ -298,10 +298,74 @@ class CryptConfig {
         if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_aes256gcm_encrypt_host: ") + pbs_strerror(rc));
         return out;
     }
+    // Opens what encrypt_host seals: the plaintext and `ok` true, or an empty vector and `ok`
+    // false when the tag does not match (nothing unauthenticated is returned)
+    std::vector<uint8_t> decrypt_host(const std::array<uint8_t, 16>& iv, const uint8_t* data, size_t len,
+                                      const std::array<uint8_t, 16>& tag, bool& ok) const {
+        std::vector<uint8_t> out(len);
+        const int rc = pbs_aes256gcm_decrypt_host(h_, iv.data(), data, len, tag.data(), out.data());
+        if (rc != PBS_OK && rc != PBS_ERR_TAG)
+            throw std::runtime_error(std::string("pbs_aes256gcm_decrypt_host: ") + pbs_strerror(rc));
+        ok = rc == PBS_OK;
+        if (!ok) out.clear();
+        return out;
+    }
 
   private:
     pbs_crypt_config* h_ = nullptr;
 };
+
+// DataBlob::load_from_reader + decode (+ verify_unencrypted's length) of one blob on the host
+// (pbs_blob_decode_host): the payload -- chunk bytes, or the zstd frame of a compressed kind,
+// which the caller inflates -- with the blob's kind (PBS_BLOB_KIND_*) and status
+// (PBS_BLOB_ST_*: the first check that fails).  `crypt`, `expect_digest`, `expect_size`: null
+// where there is none.
+struct DecodedBlob {
+    std::vector<uint8_t> payload;
+    uint8_t kind = PBS_BLOB_KIND_NONE;
+    uint8_t status = PBS_BLOB_ST_OK;
+};
+inline DecodedBlob blob_decode_host(const uint8_t* blob, size_t len, const CryptConfig* crypt = nullptr,
+                                    const Digest* expect_digest = nullptr, const uint64_t* expect_size = nullptr) {
+    DecodedBlob r;
+    r.payload.resize(len);
+    size_t n = 0;
+    const int rc = pbs_blob_decode_host(blob, len, crypt ? crypt->handle() : nullptr,
+                                        expect_digest ? expect_digest->data() : nullptr, expect_size,
+                                        r.payload.data(), r.payload.size(), &n, &r.kind, &r.status);
+    if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_blob_decode_host: ") + pbs_strerror(rc));
+    r.payload.resize(n);
+    return r;
+}
+
+// The same for n blobs [offsets[i], offsets[i+1]) of a device buffer, any mix of kinds, on the
+// GPU (pbs_blob_decode_device): the payloads back to back at `out_dev` (out_cap >=
+// pbs_blob_decode_bound), payload i at [out_offsets[i], out_offsets[i+1]).  `expect_digests`
+// (empty or n; kinds 0 and 2) and `expect_sizes` (empty or n; kind 0).  A bad blob is a status,
+// never an exception; a failed encrypted blob leaves zeros in the output.
+struct DecodedBlobs {
+    std::vector<uint64_t> out_offsets;
+    std::vector<uint8_t> kinds, status;
+    pbs_blob_decode_timing timing;
+};
+inline DecodedBlobs blob_decode_device(const uint8_t* blobs_dev, const std::vector<uint64_t>& offsets,
+                                       const CryptConfig* crypt, uint8_t* out_dev, size_t out_cap,
+                                       const std::vector<Digest>& expect_digests = {},
+                                       const std::vector<uint64_t>& expect_sizes = {}, void* hip_stream = nullptr) {
+    const size_t n = offsets.size() > 1 ? offsets.size() - 1 : 0;
+    if ((!expect_digests.empty() && expect_digests.size() != n) || (!expect_sizes.empty() && expect_sizes.size() != n))
+        throw std::invalid_argument("expectations must hold one entry per blob");
+    DecodedBlobs r;
+    r.out_offsets.assign(n + 1, 0);
+    r.kinds.resize(n);
+    r.status.resize(n);
+    const int rc = pbs_blob_decode_device(blobs_dev, offsets.data(), n, crypt ? crypt->handle() : nullptr,
+                                          expect_digests.empty() ? nullptr : expect_digests[0].data(),
+                                          expect_sizes.empty() ? nullptr : expect_sizes.data(), out_dev, out_cap,
+                                          r.out_offsets.data(), r.kinds.data(), r.status.data(), &r.timing, hip_stream);
+    if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_blob_decode_device: ") + pbs_strerror(rc));
+    return r;
+}
 
 // DataBlob::encode(chunk, Some(config), compress) of every chunk [bounds[i], bounds[i+1]) of a
 // device-resident stream, on the GPU (pbs_blob_encode_chunks_encrypted_device): the blobs

@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = (
     "pbs_crypt_config_new", "pbs_crypt_config_id_key", "pbs_crypt_config_free", "pbs_aes256gcm_encrypt_host",
     "pbs_blob_encode_chunks_encrypted_device", "pbs_blob_encode_spans_encrypted_device",
     "pbs_blob_stream_bound_encrypted", "pbs_upload_stream_host_crypt",
+    # reading blobs (include/pbs_blob.h: CRC, AES-256-GCM open, digests)
+    "pbs_blob_decode_device", "pbs_blob_decode_bound", "pbs_aes256gcm_decrypt_host", "pbs_blob_decode_host",
 )
 
 
@@ -127,6 +129,18 @@ class BlobEncodeTimingCrypt(ctypes.Structure):
         d["encrypt_ms"] = self.encrypt_ms
         d["gcm_segments"] = self.gcm_segments
         return d
+
+
+class BlobDecodeTiming(ctypes.Structure):
+    _fields_ = [
+        ("total_ms", ctypes.c_double), ("classify_ms", ctypes.c_double), ("crc_ms", ctypes.c_double),
+        ("decrypt_ms", ctypes.c_double), ("digest_ms", ctypes.c_double),
+        ("bytes_in", ctypes.c_uint64), ("bytes_out", ctypes.c_uint64),
+        ("gcm_segments", ctypes.c_uint64), ("failed", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class UploadTiming(ctypes.Structure):
@@ -242,6 +256,10 @@ def lib():
         "pbs_upload_stream_host_crypt": ([sz, p, sz, sz, p, i, p, sz, i, p, p, p, sz, ctypes.POINTER(sz),
                                           p, sz, p, p, ctypes.POINTER(UploadTiming),
                                           ctypes.POINTER(ctypes.c_double)], i),
+        "pbs_blob_decode_device": ([p, p, sz, p, p, p, p, sz, p, p, p, ctypes.POINTER(BlobDecodeTiming), p], i),
+        "pbs_blob_decode_bound": ([p, sz], sz),
+        "pbs_aes256gcm_decrypt_host": ([p, p, p, sz, p, p], i),
+        "pbs_blob_decode_host": ([p, sz, p, p, p, p, sz, ctypes.POINTER(sz), p, p], i),
         "pbs_zstd_frame_bound": ([sz], sz),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
@@ -759,6 +777,20 @@ class CryptConfig:
             raise ChunkerError(rc, "pbs_aes256gcm_encrypt_host")
         return out.tobytes(), bytes(tag)
 
+    def decrypt_host(self, iv, data, tag) -> bytes:
+        """pbs_aes256gcm_decrypt_host: the plaintext of ciphertext ``data`` under a 16-byte IV;
+        raises ChunkerError(PBS_ERR_TAG) when the 16-byte ``tag`` does not match."""
+        ivb, tagb = bytes(iv), bytes(tag)
+        if len(ivb) != 16 or len(tagb) != 16:
+            raise ValueError("the IV and the tag must be 16 bytes each")
+        a = _as_u8(data)
+        out = np.empty(a.size, dtype=np.uint8)
+        rc = lib().pbs_aes256gcm_decrypt_host(self.handle, ctypes.create_string_buffer(ivb, 16), _ptr(a), a.size,
+                                              ctypes.create_string_buffer(tagb, 16), _ptr(out))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_aes256gcm_decrypt_host")
+        return out.tobytes()
+
     def close(self):
         if self._h is not None:
             lib().pbs_crypt_config_free(self._h)
@@ -858,6 +890,74 @@ def blob_encode_spans_device(dev_ptr: int, data_len: int, spans, blobs_dev: int,
     if rc != PBS_OK:
         raise ChunkerError(rc, "pbs_blob_encode_spans_device")
     return offs, crcs, comp, t.as_dict()
+
+
+PBS_ERR_TAG = -7  # pbs_aes256gcm_decrypt_host: tag mismatch
+BLOB_KIND_UNCOMPRESSED, BLOB_KIND_COMPRESSED, BLOB_KIND_ENCRYPTED, BLOB_KIND_ENCR_COMPR = 0, 1, 2, 3
+BLOB_KIND_NONE = 255  # the magic is absent or unknown
+(BLOB_ST_OK, BLOB_ST_TOO_SMALL, BLOB_ST_BAD_MAGIC, BLOB_ST_BAD_CRC, BLOB_ST_NO_CONFIG, BLOB_ST_BAD_TAG,
+ BLOB_ST_BAD_DIGEST, BLOB_ST_BAD_SIZE) = range(8)
+
+
+def blob_decode_bound(blob_offsets) -> int:
+    """pbs_blob_decode_bound: the most payload bytes the blobs at these offsets can hold."""
+    b = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64))
+    return int(lib().pbs_blob_decode_bound(b.ctypes.data, max(0, b.size - 1)))
+
+
+def _expect_args(n: int, expect_digests, expect_sizes):
+    dg = sz = None
+    if expect_digests is not None:
+        dg = np.ascontiguousarray(np.asarray(expect_digests, dtype=np.uint8)).reshape(-1)
+        if dg.size != 32 * n:
+            raise ValueError(f"expect_digests holds {dg.size} bytes, {n} blobs need {32 * n}")
+    if expect_sizes is not None:
+        sz = np.ascontiguousarray(np.asarray(expect_sizes, dtype=np.uint64)).reshape(-1)
+        if sz.size != n:
+            raise ValueError(f"expect_sizes holds {sz.size} values for {n} blobs")
+    return dg, sz
+
+
+def blob_decode_device(blobs_dev: int, blob_offsets, out_dev: int, out_cap: int, crypt=None,
+                       expect_digests=None, expect_sizes=None, hip_stream: int = 0):
+    """pbs_blob_decode_device: load, verify and open the blob images [blob_offsets[i],
+    blob_offsets[i+1]) at device address blobs_dev (any mix of the four kinds); the payloads
+    -- chunk bytes, or the zstd frame of a compressed kind -- go back to back to out_dev.
+    ``crypt``: a CryptConfig or None; ``expect_digests``: None or (n, 32) bytes (kinds 0 and 2);
+    ``expect_sizes``: None or n lengths (kind 0).  Returns (out_offsets (n + 1), kinds (n),
+    status (n, BLOB_ST_*), timing dict).  A bad blob is a status, never an exception."""
+    b = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64))
+    n = max(0, b.size - 1)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    kinds = np.empty(n, dtype=np.uint8)
+    status = np.empty(n, dtype=np.uint8)
+    dg, sz = _expect_args(n, expect_digests, expect_sizes)
+    t = BlobDecodeTiming()
+    rc = lib().pbs_blob_decode_device(
+        ctypes.c_void_p(blobs_dev), b.ctypes.data, n, crypt.handle if crypt is not None else None,
+        None if dg is None else _ptr(dg), None if sz is None else _ptr(sz), ctypes.c_void_p(out_dev), out_cap,
+        offs.ctypes.data, _ptr(kinds), _ptr(status), ctypes.byref(t), ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_blob_decode_device")
+    return offs, kinds, status, t.as_dict()
+
+
+def blob_decode_host(blob, crypt=None, expect_digest=None, expect_size=None):
+    """pbs_blob_decode_host: one blob on the host; (payload bytes, kind, status)."""
+    a = _as_u8(blob)
+    out = np.zeros(max(a.size, 1), dtype=np.uint8)
+    olen = ctypes.c_size_t(0)
+    kind, status = ctypes.c_uint8(0), ctypes.c_uint8(0)
+    dg = None if expect_digest is None else ctypes.create_string_buffer(bytes(expect_digest), 32)
+    if expect_digest is not None and len(bytes(expect_digest)) != 32:
+        raise ValueError("the expected digest must be 32 bytes")
+    sz = None if expect_size is None else ctypes.byref(ctypes.c_uint64(int(expect_size)))
+    rc = lib().pbs_blob_decode_host(_ptr(a), a.size, crypt.handle if crypt is not None else None, dg, sz,
+                                    out.ctypes.data, out.size, ctypes.byref(olen), ctypes.byref(kind),
+                                    ctypes.byref(status))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_blob_decode_host")
+    return out[:olen.value].tobytes(), int(kind.value), int(status.value)
 
 
 def debug_arena_allocs() -> int:

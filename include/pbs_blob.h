@@ -170,8 +170,8 @@ size_t pbs_blob_stream_bound_encrypted(const uint64_t *bounds, size_t n);
  * and 2 only -- SHA-256(payload), for kind 2 SHA-256(payload || id_key) -- and `expect_sizes`
  * (NULL or n host values) for kind 0 only (verify_unencrypted returns Ok for encrypted blobs).
  * FOR KINDS 1 AND 3 THE DIGEST AND THE SIZE BELONG TO THE INFLATED DATA: the call stops at
- * OK after CRC and tag, and the caller inflates the frame it gets and checks the digest with
- * the digest calls of pbs_digest.h.
+ * OK after CRC and tag and hands the frame back; pbs_blob_decode_inflate_device (below)
+ * inflates it into the caller's slot and checks digest and size there.
  *
  * No unauthenticated plaintext is released: the output bytes of every encrypted blob whose
  * status is not OK are zero when the call returns.  (An unencrypted blob that fails keeps
@@ -233,6 +233,104 @@ int pbs_aes256gcm_decrypt_host(const pbs_crypt_config *cfg, const uint8_t iv[16]
 int pbs_blob_decode_host(const uint8_t *blob, size_t len, const pbs_crypt_config *cfg,
                          const uint8_t *expect_digest, const uint64_t *expect_size, uint8_t *out,
                          size_t cap, size_t *out_len, uint8_t *kind, uint8_t *status);
+
+/* ---- Inflating zstd frames: `zstd::stream::decode_all` (data_blob.rs:214, :238) ----
+ *
+ * A decoder of the format (RFC 8878), not the inverse of this library's encoder: it reads
+ * what libzstd writes at any level -- frames without a content size and with a window
+ * descriptor (`copy_encode`, data_blob.rs:151), 128 KiB blocks, raw / RLE / compressed blocks,
+ * raw, RLE, Huffman (1 and 4 streams, direct and FSE-described weights) and treeless
+ * literals, predefined, RLE, FSE-described and repeated sequence tables.
+ *
+ * Per frame: PBS_ZST_OK; BAD_FRAME (corrupt or truncated, bytes left after the last block and
+ * its optional checksum field, a block or literals size above 128 KiB or above the window,
+ * an offset reaching before the frame's first byte); TOO_LARGE (the content does not fit the
+ * slot -- also a content size in the header above the slot, found before anything is
+ * written); UNSUPPORTED (dictionary id != 0, window above 128 MiB, a skippable frame, a
+ * second frame after the first).  A bad frame is data: the call returns PBS_OK, and no
+ * frame's outcome depends on another's.
+ *
+ * A Content_Checksum field is CONSUMED AND NOT VERIFIED: in this system the chunk digest is
+ * the integrity check, and the reference's writers do not set the flag.
+ *
+ * A frame is decoded block by block; a block is checked completely before its first byte is
+ * written, so `out_len` is the content of the good blocks before the first bad one. */
+#define PBS_ZST_OK 0
+#define PBS_ZST_BAD_FRAME 1
+#define PBS_ZST_TOO_LARGE 2
+#define PBS_ZST_UNSUPPORTED 3
+#define PBS_ZSTD_SIZE_UNKNOWN (~(uint64_t)0)
+
+/* The serial host decoder over the same format code as the kernel (csrc/zstd_dec.h): the
+ * mirror the GPU is compared against; not a fast path.  `out` holds `cap` bytes. */
+int pbs_zstd_inflate_host(const uint8_t *frame, size_t len, uint8_t *out, size_t cap, size_t *out_len,
+                          uint8_t *status);
+/* The frame header's content size, or PBS_ZSTD_SIZE_UNKNOWN when it carries none.
+ * PBS_ERR_ARG when [frame, frame + len) holds no readable zstd frame header. */
+int pbs_zstd_frame_content_size(const uint8_t *frame, size_t len, uint64_t *size);
+
+typedef struct {
+    double total_ms;   /* call entry .. outputs on the host */
+    double inflate_ms; /* the inflate launch (HIP events) */
+    uint64_t bytes_in, bytes_out, frames;
+    uint64_t failed;     /* frames whose status is not OK */
+    uint64_t workgroups; /* workgroups launched: min(frames, CUs x the resident workgroups per CU) */
+} pbs_zstd_inflate_timing;
+
+/* n frames on the GPU, one workgroup per frame.  Frame i is [frame_offsets[i],
+ * frame_offsets[i+1]) of `frames_dev` (device; offsets on the host, n + 1 ascending values
+ * at any alignment) and is never written.  Its content goes to the caller's slot
+ * [out_offsets[i], out_offsets[i+1]) of `out_dev` (host offsets, n + 1 ascending: the caller
+ * sizes the slots, as libzstd's streaming frames carry no size and the index knows every
+ * chunk's length); out_lens[i] (host, n) is what was produced.  Slot bytes past it, and
+ * everything outside the slots, stay untouched.  status[i] (host, n): PBS_ZST_*.
+ * Device scratch comes from a work area kept between calls until pbs_blob_encode_release;
+ * all launches go on `hip_stream`; synchronous. */
+int pbs_zstd_inflate_device(const uint8_t *frames_dev, const uint64_t *frame_offsets, size_t n,
+                            uint8_t *out_dev, const uint64_t *out_offsets, uint64_t *out_lens,
+                            uint8_t *status, pbs_zstd_inflate_timing *timing, void *hip_stream);
+
+/* ---- The read path, finished: load, open, inflate and verify in one call ----
+ *
+ * pbs_blob_decode_device's inputs (blobs of mixed kinds, `cfg` or NULL, `expect_digests` NULL or
+ * 32 n host bytes) plus `chunk_sizes` (n host values, required: the index knows every chunk's
+ * length): blob i's chunk goes to the slot [out_offsets[i], out_offsets[i+1]) of `out_dev`,
+ * out_offsets being the running sum of chunk_sizes (written by the call, n + 1 host values;
+ * out_cap below their sum: PBS_ERR_CAPACITY before anything is written); out_lens[i] (host,
+ * n) is what the slot holds.  Stages: classify / CRC / GCM open as in pbs_blob_decode_device
+ * (packed into device scratch); kinds 0 and 2 copied, kinds 1 and 3 inflated into the slots;
+ * SHA-256 over [slot, slot + out_lens) for ALL FOUR kinds (keyed with id_key for 2 and 3)
+ * against expect_digests; verdict; wipe.
+ *
+ * status[i]: the first failing check in the reference's order -- load (size, magic, CRC),
+ * decrypt (config, tag), decode_all (BAD_FRAME, UNSUPPORTED_FRAME), verify_digest, then the
+ * length: with `sizes_exact` != 0 a length != chunk_sizes[i] is BAD_SIZE for kinds 0 and 1
+ * (verify_unencrypted, data_blob.rs:324, checks both unencrypted magics and returns Ok for
+ * encrypted ones).  Content that overflows its slot is BAD_DIGEST when digests are given (a
+ * message of another length cannot have that digest, and the reference would fail there
+ * first), else BAD_SIZE -- for every kind; the slot then holds the content's first bytes
+ * (kinds 0 and 2) or the blocks that fitted (kinds 1 and 3).
+ *
+ * The whole slot of an encrypted blob whose status is not OK is zero when the call returns
+ * (out_lens 0) -- a kind 3 that fails in the inflater or at the digest included.  An
+ * unencrypted blob that fails keeps what was written.  Slot bytes past out_lens are not
+ * written otherwise.  Synchronous; scratch from the decode work areas
+ * (pbs_blob_encode_release). */
+#define PBS_BLOB_ST_BAD_FRAME 8         /* kinds 1 and 3: PBS_ZST_BAD_FRAME (decode_all fails) */
+#define PBS_BLOB_ST_UNSUPPORTED_FRAME 9 /* kinds 1 and 3: PBS_ZST_UNSUPPORTED */
+
+typedef struct {
+    pbs_blob_decode_timing base; /* digest_ms: digests of all kinds, verdicts, wipe */
+    double inflate_ms;           /* slot copies + the inflate launch (HIP events) */
+    uint64_t frames;             /* frames handed to the inflater */
+} pbs_blob_decode_inflate_timing;
+
+int pbs_blob_decode_inflate_device(const uint8_t *blobs_dev, const uint64_t *blob_offsets, size_t n,
+                                   const pbs_crypt_config *cfg, const uint8_t *expect_digests,
+                                   const uint64_t *chunk_sizes, int sizes_exact, uint8_t *out_dev,
+                                   size_t out_cap, uint64_t *out_offsets, uint64_t *out_lens,
+                                   uint8_t *kinds, uint8_t *status, pbs_blob_decode_inflate_timing *timing,
+                                   void *hip_stream);
 
 #ifdef __cplusplus
 }

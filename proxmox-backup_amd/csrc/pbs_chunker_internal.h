@@ -150,6 +150,16 @@ hipError_t launch_crc32_spans(const uint8_t* data, const uint64_t* spans_dev, co
                               uint64_t n, uint32_t* out, hipStream_t st);
 // pbs_decode.hip: frees the idle work areas of pbs_blob_decode_device (pbs_blob_encode_release)
 void decode_release();
+// pbs_inflate.hip: the zstd inflater's launch on `st` (offsets, order, lengths and status in
+// device memory; order_dev: a permutation of 0..n-1, longest frame first).  Takes 2 arena
+// slots from `slot0`; *grid_out: the workgroups launched.  inflate_release frees the idle work areas of pbs_zstd_inflate_device.
+class DevArena;
+namespace inflate {
+int inflate_async(const uint8_t* frames_dev, const uint64_t* foff_dev, const uint64_t* ooff_dev,
+                  const uint32_t* order_dev, size_t n, uint8_t* out_dev, uint64_t* lens_dev, uint8_t* status_dev,
+                  DevArena& ar, unsigned slot0, int ncu, hipStream_t st, unsigned* grid_out = nullptr);
+void inflate_release();
+}  // namespace inflate
 // pbs_crypt.hip: AES-256-GCM in place over the payloads of n blob images (plaintext at
 // blob + 44; blob i = [boff[i], boff[i+1]), offsets on host and device), IV and tag into the
 // headers; asynchronous on `st`.  Takes 5 arena slots from `slot0`; `hs` holds the host

@@ -343,7 +343,10 @@ void host_tag(const KeyDev& k, const uint32_t j0w[4], const uint8_t* ct, size_t 
 }  // namespace
 }  // namespace dec
 
-void decode_release() { dec::dpool().clear(); }
+void decode_release() {
+    dec::dpool().clear();
+    inflate::inflate_release();
+}
 
 }  // namespace pbs
 

@@ -367,6 +367,72 @@ inline DecodedBlobs blob_decode_device(const uint8_t* blobs_dev, const std::vect
     return r;
 }
 
+// zstd frames (`zstd::stream::decode_all`).  zstd_frame_content_size: the header's content size,
+// PBS_ZSTD_SIZE_UNKNOWN when it carries none.  zstd_inflate_host: the serial mirror of the GPU
+// inflater -- `cap` bytes of room, the status PBS_ZST_* in `status`.  zstd_inflate_device: frame
+// i = [frame_offsets[i], frame_offsets[i+1]) of a device buffer into the caller's slot
+// [out_offsets[i], out_offsets[i+1]) of `out_dev`; a bad frame is a status, never an exception.
+inline uint64_t zstd_frame_content_size(const uint8_t* frame, size_t len) {
+    uint64_t v = 0;
+    if (pbs_zstd_frame_content_size(frame, len, &v) != PBS_OK) throw std::invalid_argument("no zstd frame header");
+    return v;
+}
+inline std::vector<uint8_t> zstd_inflate_host(const uint8_t* frame, size_t len, size_t cap, uint8_t& status) {
+    std::vector<uint8_t> out(cap);
+    size_t n = 0;
+    const int rc = pbs_zstd_inflate_host(frame, len, out.data(), cap, &n, &status);
+    if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_zstd_inflate_host: ") + pbs_strerror(rc));
+    out.resize(n);
+    return out;
+}
+struct InflatedFrames {
+    std::vector<uint64_t> out_lens;
+    std::vector<uint8_t> status;
+    pbs_zstd_inflate_timing timing;
+};
+inline InflatedFrames zstd_inflate_device(const uint8_t* frames_dev, const std::vector<uint64_t>& frame_offsets,
+                                          uint8_t* out_dev, const std::vector<uint64_t>& out_offsets,
+                                          void* hip_stream = nullptr) {
+    const size_t n = frame_offsets.size() > 1 ? frame_offsets.size() - 1 : 0;
+    if (out_offsets.size() != n + 1) throw std::invalid_argument("out_offsets must hold one slot per frame");
+    InflatedFrames r;
+    r.out_lens.assign(n, 0);
+    r.status.assign(n, 0);
+    const int rc = pbs_zstd_inflate_device(frames_dev, frame_offsets.data(), n, out_dev, out_offsets.data(),
+                                           r.out_lens.data(), r.status.data(), &r.timing, hip_stream);
+    if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_zstd_inflate_device: ") + pbs_strerror(rc));
+    return r;
+}
+
+// The read path in one call (pbs_blob_decode_inflate_device): blob i's chunk -- copied, opened,
+// inflated -- in the slot of chunk_sizes[i] bytes at out_offsets[i] of `out_dev`, its length in
+// out_lens[i]; `expect_digests` (empty or n) is checked for all four kinds.
+struct InflatedBlobs {
+    std::vector<uint64_t> out_offsets, out_lens;
+    std::vector<uint8_t> kinds, status;
+    pbs_blob_decode_inflate_timing timing;
+};
+inline InflatedBlobs blob_decode_inflate_device(const uint8_t* blobs_dev, const std::vector<uint64_t>& offsets,
+                                                const CryptConfig* crypt, const std::vector<uint64_t>& chunk_sizes,
+                                                uint8_t* out_dev, size_t out_cap,
+                                                const std::vector<Digest>& expect_digests = {},
+                                                bool sizes_exact = false, void* hip_stream = nullptr) {
+    const size_t n = offsets.size() > 1 ? offsets.size() - 1 : 0;
+    if (chunk_sizes.size() != n || (!expect_digests.empty() && expect_digests.size() != n))
+        throw std::invalid_argument("chunk_sizes and expectations must hold one entry per blob");
+    InflatedBlobs r;
+    r.out_offsets.assign(n + 1, 0);
+    r.out_lens.assign(n, 0);
+    r.kinds.resize(n);
+    r.status.resize(n);
+    const int rc = pbs_blob_decode_inflate_device(
+        blobs_dev, offsets.data(), n, crypt ? crypt->handle() : nullptr,
+        expect_digests.empty() ? nullptr : expect_digests[0].data(), chunk_sizes.data(), sizes_exact ? 1 : 0, out_dev,
+        out_cap, r.out_offsets.data(), r.out_lens.data(), r.kinds.data(), r.status.data(), &r.timing, hip_stream);
+    if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_blob_decode_inflate_device: ") + pbs_strerror(rc));
+    return r;
+}
+
 // DataBlob::encode(chunk, Some(config), compress) of every chunk [bounds[i], bounds[i+1]) of a
 // device-resident stream, on the GPU (pbs_blob_encode_chunks_encrypted_device): the blobs
 // back to back at `blobs_dev` (blobs_cap >= pbs_blob_stream_bound_encrypted), blob i at

@@ -68,6 +68,9 @@ EXPORTED_SYMBOLS = (
     "pbs_blob_stream_bound_encrypted", "pbs_upload_stream_host_crypt",
     # reading blobs (include/pbs_blob.h: CRC, AES-256-GCM open, digests)
     "pbs_blob_decode_device", "pbs_blob_decode_bound", "pbs_aes256gcm_decrypt_host", "pbs_blob_decode_host",
+    # inflating zstd frames (include/pbs_blob.h)
+    "pbs_zstd_inflate_device", "pbs_zstd_inflate_host", "pbs_zstd_frame_content_size",
+    "pbs_blob_decode_inflate_device",
 )
 
 
@@ -141,6 +144,27 @@ class BlobDecodeTiming(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ZstdInflateTiming(ctypes.Structure):
+    _fields_ = [
+        ("total_ms", ctypes.c_double), ("inflate_ms", ctypes.c_double),
+        ("bytes_in", ctypes.c_uint64), ("bytes_out", ctypes.c_uint64), ("frames", ctypes.c_uint64),
+        ("failed", ctypes.c_uint64), ("workgroups", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BlobDecodeInflateTiming(ctypes.Structure):
+    _fields_ = [("base", BlobDecodeTiming), ("inflate_ms", ctypes.c_double), ("frames", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = self.base.as_dict()
+        d["inflate_ms"] = self.inflate_ms
+        d["frames"] = self.frames
+        return d
 
 
 class UploadTiming(ctypes.Structure):
@@ -260,6 +284,11 @@ def lib():
         "pbs_blob_decode_bound": ([p, sz], sz),
         "pbs_aes256gcm_decrypt_host": ([p, p, p, sz, p, p], i),
         "pbs_blob_decode_host": ([p, sz, p, p, p, p, sz, ctypes.POINTER(sz), p, p], i),
+        "pbs_blob_decode_inflate_device": ([p, p, sz, p, p, p, i, p, sz, p, p, p, p,
+                                            ctypes.POINTER(BlobDecodeInflateTiming), p], i),
+        "pbs_zstd_inflate_device": ([p, p, sz, p, p, p, p, ctypes.POINTER(ZstdInflateTiming), p], i),
+        "pbs_zstd_inflate_host": ([p, sz, p, sz, ctypes.POINTER(sz), p], i),
+        "pbs_zstd_frame_content_size": ([p, sz, ctypes.POINTER(u64)], i),
         "pbs_zstd_frame_bound": ([sz], sz),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
@@ -958,6 +987,85 @@ def blob_decode_host(blob, crypt=None, expect_digest=None, expect_size=None):
     if rc != PBS_OK:
         raise ChunkerError(rc, "pbs_blob_decode_host")
     return out[:olen.value].tobytes(), int(kind.value), int(status.value)
+
+
+# ---- inflating zstd frames (include/pbs_blob.h) ----
+ZST_OK, ZST_BAD_FRAME, ZST_TOO_LARGE, ZST_UNSUPPORTED = range(4)
+ZSTD_SIZE_UNKNOWN = (1 << 64) - 1
+
+
+def zstd_frame_content_size(frame) -> Optional[int]:
+    """pbs_zstd_frame_content_size: the header's content size, None when it carries none;
+    ValueError when there is no readable frame header."""
+    a = _as_u8(frame)
+    v = ctypes.c_uint64(0)
+    rc = lib().pbs_zstd_frame_content_size(_ptr(a), a.size, ctypes.byref(v))
+    if rc != PBS_OK:
+        raise ValueError("no zstd frame header")
+    return None if v.value == ZSTD_SIZE_UNKNOWN else int(v.value)
+
+
+def zstd_inflate_host(frame, cap: int):
+    """pbs_zstd_inflate_host: the serial mirror of the GPU inflater; (bytes produced into a
+    buffer of ``cap`` bytes, status ZST_*)."""
+    a = _as_u8(frame)
+    out = np.zeros(max(int(cap), 1), dtype=np.uint8)
+    olen = ctypes.c_size_t(0)
+    status = ctypes.c_uint8(0)
+    rc = lib().pbs_zstd_inflate_host(_ptr(a), a.size, out.ctypes.data, int(cap), ctypes.byref(olen),
+                                     ctypes.byref(status))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_zstd_inflate_host")
+    return out[:olen.value].tobytes(), int(status.value)
+
+
+def zstd_inflate_device(frames_dev: int, frame_offsets, out_dev: int, out_offsets, hip_stream: int = 0):
+    """pbs_zstd_inflate_device: frame i = [frame_offsets[i], frame_offsets[i+1]) at device
+    address frames_dev, inflated into the slot [out_offsets[i], out_offsets[i+1]) of out_dev.
+    Returns (out_lens (n), status (n, ZST_*), timing dict).  A bad frame is a status."""
+    f = np.ascontiguousarray(np.asarray(frame_offsets, dtype=np.uint64))
+    o = np.ascontiguousarray(np.asarray(out_offsets, dtype=np.uint64))
+    n = max(0, f.size - 1)
+    if o.size != n + 1:
+        raise ValueError(f"out_offsets holds {o.size} values, {n} frames need {n + 1}")
+    lens = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.uint8)
+    t = ZstdInflateTiming()
+    rc = lib().pbs_zstd_inflate_device(ctypes.c_void_p(frames_dev), f.ctypes.data, n, ctypes.c_void_p(out_dev),
+                                       o.ctypes.data, _ptr(lens), _ptr(status), ctypes.byref(t),
+                                       ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_zstd_inflate_device")
+    return lens, status, t.as_dict()
+
+
+BLOB_ST_BAD_FRAME, BLOB_ST_UNSUPPORTED_FRAME = 8, 9
+
+
+def blob_decode_inflate_device(blobs_dev: int, blob_offsets, out_dev: int, out_cap: int, chunk_sizes, crypt=None,
+                               expect_digests=None, sizes_exact: bool = False, hip_stream: int = 0):
+    """pbs_blob_decode_inflate_device: the read path in one call -- load, verify, open, inflate
+    and digest the blob images (any mix of the four kinds); chunk i goes to the slot of
+    ``chunk_sizes[i]`` bytes at out_offsets[i] of out_dev.  ``expect_digests``: None or (n, 32)
+    bytes, checked for all four kinds.  Returns (out_offsets (n + 1), out_lens (n), kinds (n),
+    status (n, BLOB_ST_*), timing dict).  A bad blob is a status, never an exception."""
+    b = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64))
+    n = max(0, b.size - 1)
+    dg, cs = _expect_args(n, expect_digests, chunk_sizes)
+    if cs is None:
+        raise ValueError("chunk_sizes is required")
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    lens = np.zeros(n, dtype=np.uint64)
+    kinds = np.empty(n, dtype=np.uint8)
+    status = np.empty(n, dtype=np.uint8)
+    t = BlobDecodeInflateTiming()
+    rc = lib().pbs_blob_decode_inflate_device(
+        ctypes.c_void_p(blobs_dev), b.ctypes.data, n, crypt.handle if crypt is not None else None,
+        None if dg is None else _ptr(dg), _ptr(cs), 1 if sizes_exact else 0, ctypes.c_void_p(out_dev), out_cap,
+        offs.ctypes.data, _ptr(lens), _ptr(kinds), _ptr(status), ctypes.byref(t), ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_blob_decode_inflate_device")
+    return offs, lens, kinds, status, t.as_dict()
 
 
 def debug_arena_allocs() -> int:

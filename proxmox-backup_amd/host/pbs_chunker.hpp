@@ -5,6 +5,7 @@
 //   pbs::ChunkStream        pbs-client/src/chunk_stream.rs:12-78  (pull iterator of chunks)
 //   pbs::DynamicChunkWriter pbs-datastore/src/dynamic_index.rs:397-523 (write / close)
 //   pbs::DynamicIndexWriter pbs-datastore/src/dynamic_index.rs:297-391 (add_chunk / close)
+//   pbs::DynamicIndexReader pbs-datastore/src/dynamic_index.rs:82-275 (open / chunk_from_offset)
 //   pbs::digest_chunks_device  DataChunkBuilder::digest (data_blob.rs:516-536) per chunk, GPU
 //   pbs::sha256             openssl::sha::sha256 (host; index checksum)
 //   pbs::crc32_chunks_device DataBlob::compute_crc (data_blob.rs:70-75) per chunk, GPU
@@ -37,6 +38,7 @@
 #include "pbs_chunker.h"
 #include "pbs_blob.h"
 #include "pbs_digest.h"
+#include "pbs_restore.h"
 
 namespace pbs {
 
@@ -547,6 +549,76 @@ class DynamicIndexWriter {
     std::vector<uint64_t> ends_;
     std::vector<uint8_t> digests_;
     bool closed_ = false;
+};
+
+// DynamicIndexReader (dynamic_index.rs:82-275) over pbs_didx_parse: from the bytes of a .didx
+// image or from a file.  Throws where the reference's `new` bails (short image, wrong magic,
+// ragged body) and for chunk ends that decrease.  index_csum is the header's checksum,
+// compute_csum() the one over the entries; opening does not compare them.
+struct ChunkReadInfo {
+    uint64_t start, end;
+    Digest digest;
+};
+class DynamicIndexReader {
+  public:
+    DynamicIndexReader(const uint8_t* image, size_t len) { parse(image, len); }
+    explicit DynamicIndexReader(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) throw std::runtime_error("Unable to open dynamic index " + path);
+        std::vector<uint8_t> image;
+        uint8_t buf[65536];
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) image.insert(image.end(), buf, buf + k);
+        std::fclose(f);
+        parse(image.data(), image.size());
+    }
+
+    std::array<uint8_t, 16> uuid{};
+    int64_t ctime = 0;
+    Digest index_csum{};
+    size_t size = 0;  // bytes of the image
+
+    size_t index_count() const { return ends_.size(); }
+    uint64_t index_bytes() const { return ends_.empty() ? 0 : ends_.back(); }
+    uint64_t chunk_end(size_t pos) const {
+        if (pos >= ends_.size()) throw std::out_of_range("chunk index out of range");
+        return ends_[pos];
+    }
+    std::optional<Digest> index_digest(size_t pos) const {
+        if (pos >= ends_.size()) return std::nullopt;
+        Digest d;
+        std::memcpy(d.data(), digests_.data() + 32 * pos, 32);
+        return d;
+    }
+    std::optional<ChunkReadInfo> chunk_info(size_t pos) const {
+        if (pos >= ends_.size()) return std::nullopt;
+        return ChunkReadInfo{pos ? ends_[pos - 1] : 0, ends_[pos], *index_digest(pos)};
+    }
+    // (entry, offset inside it) of an archive byte; nullopt at or past the end
+    std::optional<std::pair<size_t, uint64_t>> chunk_from_offset(uint64_t offset) const {
+        size_t idx = 0;
+        uint64_t within = 0;
+        if (pbs_didx_chunk_from_offset(ends_.data(), ends_.size(), offset, &idx, &within) != PBS_OK) return std::nullopt;
+        return std::make_pair(idx, within);
+    }
+    std::pair<Digest, uint64_t> compute_csum() const { return {csum_, index_bytes()}; }
+    const std::vector<uint64_t>& ends() const { return ends_; }
+    const std::vector<uint8_t>& digests() const { return digests_; }  // 32 bytes per entry
+
+  private:
+    void parse(const uint8_t* image, size_t len) {
+        const size_t cnt = pbs_didx_count(len);
+        const size_t cap = cnt == (size_t)-1 ? 0 : cnt;
+        ends_.resize(cap);
+        digests_.resize(32 * cap);
+        size_t n = 0;
+        const int rc = pbs_didx_parse(image, len, uuid.data(), &ctime, index_csum.data(), csum_.data(), ends_.data(),
+                                      digests_.data(), cap, &n);
+        if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_didx_parse: ") + pbs_strerror(rc));
+        size = len;
+    }
+    std::vector<uint64_t> ends_;
+    std::vector<uint8_t> digests_;
+    Digest csum_{};
 };
 
 }  // namespace pbs

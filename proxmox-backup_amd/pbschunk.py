@@ -15,6 +15,10 @@ Mirrors, with the same names, argument meaning and error behaviour:
       ``CryptConfig::compute_digest``, pbs-tools/src/crypt_config.rs:79-84).
   * ``DynamicIndexWriter(path)`` -- ``add_chunk(offset, digest)`` / ``close() -> csum``
       pbs-datastore/src/dynamic_index.rs:297-391 (.didx image built by the C library).
+  * ``DynamicIndexReader(bytes or path)`` -- ``index_count`` / ``chunk_info`` / ``chunk_from_offset`` ...
+      pbs-datastore/src/dynamic_index.rs:82-275, and ``restore_range_device`` /
+      ``restore_stream_device``: the bytes of an archive range from an index and a blob store
+      (``BufferedDynamicReader`` :544-673 over ``ReadChunk::read_chunk``; include/pbs_restore.h).
 
 The hash scan always runs on the GPU through the HIP library; there is no CPU path.
 Loading fails loudly (``ChunkerLibraryError``) when the library is missing and handle
@@ -71,6 +75,9 @@ EXPORTED_SYMBOLS = (
     # inflating zstd frames (include/pbs_blob.h)
     "pbs_zstd_inflate_device", "pbs_zstd_inflate_host", "pbs_zstd_frame_content_size",
     "pbs_blob_decode_inflate_device",
+    # restoring a .didx stream (include/pbs_restore.h)
+    "pbs_didx_count", "pbs_didx_parse", "pbs_didx_chunk_from_offset", "pbs_digest_lookup_device",
+    "pbs_digest_lookup_host", "pbs_copy_segments_device", "pbs_restore_range_device", "pbs_restore_release",
 )
 
 
@@ -165,6 +172,19 @@ class BlobDecodeInflateTiming(ctypes.Structure):
         d["inflate_ms"] = self.inflate_ms
         d["frames"] = self.frames
         return d
+
+
+class RestoreTiming(ctypes.Structure):
+    _fields_ = [
+        ("total_ms", ctypes.c_double), ("lookup_ms", ctypes.c_double), ("pack_ms", ctypes.c_double),
+        ("decode_ms", ctypes.c_double), ("scatter_ms", ctypes.c_double),
+        ("entries", ctypes.c_uint64), ("unique", ctypes.c_uint64), ("missing", ctypes.c_uint64),
+        ("failed", ctypes.c_uint64), ("blob_bytes", ctypes.c_uint64), ("decoded_bytes", ctypes.c_uint64),
+        ("out_bytes", ctypes.c_uint64), ("decode", BlobDecodeInflateTiming),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: (getattr(self, k).as_dict() if k == "decode" else getattr(self, k)) for k, _ in self._fields_}
 
 
 class UploadTiming(ctypes.Structure):
@@ -290,6 +310,14 @@ def lib():
         "pbs_zstd_inflate_host": ([p, sz, p, sz, ctypes.POINTER(sz), p], i),
         "pbs_zstd_frame_content_size": ([p, sz, ctypes.POINTER(u64)], i),
         "pbs_zstd_frame_bound": ([sz], sz),
+        "pbs_didx_count": ([sz], sz),
+        "pbs_didx_parse": ([p, sz, p, ctypes.POINTER(ctypes.c_int64), p, p, p, p, sz, ctypes.POINTER(sz)], i),
+        "pbs_didx_chunk_from_offset": ([p, sz, u64, ctypes.POINTER(sz), ctypes.POINTER(u64)], i),
+        "pbs_digest_lookup_device": ([p, sz, p, sz, p, p, ctypes.POINTER(sz), ctypes.POINTER(sz), p], i),
+        "pbs_digest_lookup_host": ([p, sz, p, sz, p, p, ctypes.POINTER(sz), ctypes.POINTER(sz)], i),
+        "pbs_copy_segments_device": ([p, p, p, p, p, sz, p], i),
+        "pbs_restore_range_device": ([p, p, sz, p, p, p, sz, p, u64, u64, p, p, ctypes.POINTER(RestoreTiming), p], i),
+        "pbs_restore_release": ([], None),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
@@ -1074,8 +1102,15 @@ def debug_arena_allocs() -> int:
 
 
 def blob_encode_release() -> None:
-    """Free the blob encoder's cached device scratch."""
+    """Free the blob encoder's cached device scratch, the decoder's and the restore calls'."""
     lib().pbs_blob_encode_release()
+    if hasattr(lib(), "pbs_restore_release"):  # (absent from an older build in an A/B run)
+        lib().pbs_restore_release()
+
+
+def restore_release() -> None:
+    """pbs_restore_release: free the idle work areas of the lookup, copy and restore calls."""
+    lib().pbs_restore_release()
 
 
 def digest_hybrid_release() -> None:
@@ -1208,6 +1243,213 @@ def read_didx(image: bytes):
     ends = ent[:, :8].copy().view("<u8").reshape(-1)
     ctime = int.from_bytes(image[24:32], "little", signed=True)
     return image[8:24], ctime, image[32:64], ends, ent[:, 8:].copy()
+
+
+# ---- restoring a .didx stream (include/pbs_restore.h) ----
+BLOB_ST_MISSING = 10           # no blob in the store carries the entry's digest
+BLOB_ST_NONE_REQUESTED = 255   # the entry lies outside the requested range
+LOOKUP_MISSING = 0xFFFFFFFF
+
+
+def didx_count(image_len: int) -> Optional[int]:
+    """pbs_didx_count: entries of an image of that many bytes; None when it is shorter than the
+    header or its body is no multiple of 40."""
+    n = int(lib().pbs_didx_count(int(image_len)))
+    return None if n == ctypes.c_size_t(-1).value else n
+
+
+def didx_parse(image, cap: Optional[int] = None):
+    """pbs_didx_parse: (uuid, ctime, header_csum, computed_csum, ends (u64), digests (n, 32)).
+    Raises ChunkerError(PBS_ERR_INVALID) for a short image, a wrong magic, a ragged body or a
+    decreasing end, and ChunkerError(PBS_ERR_CAPACITY) when ``cap`` (default: what the image
+    holds) is too small."""
+    a = _as_u8(image)
+    if cap is None:
+        cap = didx_count(a.size) or 0
+    ends = np.zeros(cap, dtype=np.uint64)
+    digests = np.zeros((cap, 32), dtype=np.uint8)
+    uuid, hc, cc = (ctypes.c_uint8 * 16)(), (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
+    ctime, n = ctypes.c_int64(0), ctypes.c_size_t(0)
+    rc = lib().pbs_didx_parse(_ptr(a), a.size, uuid, ctypes.byref(ctime), hc, cc, ends.ctypes.data if cap else None,
+                              digests.ctypes.data if cap else None, cap, ctypes.byref(n))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_didx_parse")
+    return bytes(uuid), int(ctime.value), bytes(hc), bytes(cc), ends[:n.value], digests[:n.value]
+
+
+def didx_chunk_from_offset(ends, offset: int):
+    """pbs_didx_chunk_from_offset: (entry, offset inside it), or None where the reference's
+    chunk_from_offset returns None (offset at or past the end, empty index)."""
+    e = np.ascontiguousarray(np.asarray(ends, dtype=np.uint64))
+    idx, within = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    rc = lib().pbs_didx_chunk_from_offset(e.ctypes.data if e.size else None, e.size, int(offset), ctypes.byref(idx),
+                                          ctypes.byref(within))
+    if rc == PBS_ERR_INVALID:
+        return None
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_didx_chunk_from_offset")
+    return int(idx.value), int(within.value)
+
+
+class DynamicIndexReader:
+    """dynamic_index.rs:82-275 over the C reader: built from the bytes of a .didx image or from
+    a path.  ``index_csum`` is the header's checksum and ``compute_csum()`` the one over the
+    entries; as in the reference, opening does not compare them.  ``ctime`` is the header's
+    field.  Raises ChunkerError where the reference's ``new`` bails."""
+
+    def __init__(self, source):
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as f:
+                source = f.read()
+        image = bytes(source)
+        self.size = len(image)
+        self.uuid, self.ctime, self.index_csum, self._csum, self.ends, self.digests = didx_parse(image)
+
+    def index_count(self) -> int:
+        return int(self.ends.size)
+
+    def index_bytes(self) -> int:
+        return int(self.ends[-1]) if self.ends.size else 0
+
+    def chunk_end(self, pos: int) -> int:
+        if not 0 <= pos < self.ends.size:
+            raise IndexError("chunk index out of range")
+        return int(self.ends[pos])
+
+    def index_digest(self, pos: int) -> Optional[bytes]:
+        return self.digests[pos].tobytes() if 0 <= pos < self.ends.size else None
+
+    def chunk_info(self, pos: int):
+        """(start, end, digest) of entry ``pos``, or None past the end."""
+        if not 0 <= pos < self.ends.size:
+            return None
+        return (int(self.ends[pos - 1]) if pos else 0), int(self.ends[pos]), self.digests[pos].tobytes()
+
+    def chunk_from_offset(self, offset: int):
+        return didx_chunk_from_offset(self.ends, offset)
+
+    def compute_csum(self):
+        """(checksum over the entries, the archive's length)."""
+        return self._csum, self.index_bytes()
+
+
+def _digest_rows(digests) -> np.ndarray:
+    if isinstance(digests, (list, tuple)):
+        digests = np.frombuffer(b"".join(bytes(x) for x in digests), dtype=np.uint8)
+    return np.ascontiguousarray(np.asarray(digests, dtype=np.uint8).reshape(-1, 32))
+
+
+def digest_lookup_host(digests, store):
+    """pbs_digest_lookup_host: (store_pos (n, LOOKUP_MISSING where absent), first (n), n_missing,
+    n_unique) of the index digests against the store's digest list, on the host."""
+    d, s = _digest_rows(digests), _digest_rows(store)
+    pos = np.zeros(d.shape[0], dtype=np.uint32)
+    first = np.zeros(d.shape[0], dtype=np.uint32)
+    nm, nu = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = lib().pbs_digest_lookup_host(d.ctypes.data, d.shape[0], s.ctypes.data if s.shape[0] else None, s.shape[0],
+                                      pos.ctypes.data, first.ctypes.data, ctypes.byref(nm), ctypes.byref(nu))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_digest_lookup_host")
+    return pos, first, int(nm.value), int(nu.value)
+
+
+def digest_lookup_device(digests_dev: int, n: int, store_dev: int, m: int, store_pos_dev: int, first_dev: int,
+                         hip_stream: int = 0):
+    """pbs_digest_lookup_device: all pointers device memory (n and m 32-byte digests, 16-byte
+    aligned; n u32 each for the two outputs).  Returns (n_missing, n_unique)."""
+    nm, nu = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = lib().pbs_digest_lookup_device(ctypes.c_void_p(digests_dev), n, ctypes.c_void_p(store_dev or None), m,
+                                        ctypes.c_void_p(store_pos_dev), ctypes.c_void_p(first_dev), ctypes.byref(nm),
+                                        ctypes.byref(nu), ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_digest_lookup_device")
+    return int(nm.value), int(nu.value)
+
+
+def copy_segments_device(src_dev: int, dst_dev: int, src_off, dst_off, lens, hip_stream: int = 0) -> None:
+    """pbs_copy_segments_device: segment k moves lens[k] bytes from src_dev + src_off[k] to
+    dst_dev + dst_off[k].  An overlapping destination raises ChunkerError(PBS_ERR_INVALID) with
+    nothing written."""
+    so = np.ascontiguousarray(np.asarray(src_off, dtype=np.uint64))
+    do = np.ascontiguousarray(np.asarray(dst_off, dtype=np.uint64))
+    ln = np.ascontiguousarray(np.asarray(lens, dtype=np.uint64))
+    if not so.size == do.size == ln.size:
+        raise ValueError("src_off, dst_off and lens differ in length")
+    rc = lib().pbs_copy_segments_device(ctypes.c_void_p(src_dev), ctypes.c_void_p(dst_dev), so.ctypes.data,
+                                        do.ctypes.data, ln.ctypes.data, ln.size, ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_copy_segments_device")
+
+
+def _index_arrays(index):
+    if isinstance(index, DynamicIndexReader):
+        return index.ends, index.digests
+    ends, digests = index
+    return np.ascontiguousarray(np.asarray(ends, dtype=np.uint64)), _digest_rows(digests)
+
+
+def restore_range_device(index, store_blobs_dev: int, store_offsets, store_digests, out_dev: int, offset: int = 0,
+                         length: Optional[int] = None, crypt=None, allow_bad: bool = False, hip_stream: int = 0):
+    """pbs_restore_range_device: archive bytes [offset, offset + length) of the stream that
+    ``index`` (a DynamicIndexReader, or (ends, digests)) describes, to device address out_dev.
+    The store: blob j = [store_offsets[j], store_offsets[j+1]) at device address
+    store_blobs_dev, filed under store_digests[j] ((m, 32) bytes, host).  ``length`` None: to the
+    end of the archive.  Every distinct chunk of the range is decoded and verified once.
+    Returns (status (one BLOB_ST_* per index entry, BLOB_ST_NONE_REQUESTED outside the range),
+    timing dict).  The output of an entry that is not OK is zeros; ChunkerError is raised for it
+    unless ``allow_bad``."""
+    ends, digests = _index_arrays(index)
+    n = int(ends.size)
+    if digests.shape[0] != n:
+        raise ValueError("ends and digests differ in length")
+    so = np.ascontiguousarray(np.asarray(store_offsets, dtype=np.uint64))
+    sd = _digest_rows(store_digests)
+    m = int(sd.shape[0])
+    if so.size != m + 1:
+        raise ValueError(f"store_offsets holds {so.size} values, {m} blobs need {m + 1}")
+    total = int(ends[-1]) if n else 0
+    if length is None:
+        length = max(0, total - int(offset))
+    status = np.full(n, BLOB_ST_NONE_REQUESTED, dtype=np.uint8)
+    t = RestoreTiming()
+    rc = lib().pbs_restore_range_device(
+        ends.ctypes.data if n else None, digests.ctypes.data if n else None, n, ctypes.c_void_p(store_blobs_dev or None),
+        so.ctypes.data, sd.ctypes.data if m else None, m, crypt.handle if crypt is not None else None, int(offset),
+        int(length), ctypes.c_void_p(out_dev or None), status.ctypes.data if n else None, ctypes.byref(t),
+        ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_restore_range_device")
+    if t.failed and not allow_bad:
+        bad = [(int(k), int(status[k])) for k in np.flatnonzero((status != BLOB_ST_OK) & (status != BLOB_ST_NONE_REQUESTED))]
+        raise ChunkerError(PBS_ERR_INVALID, f"restore: {t.failed} entries failed (entry, status): {bad[:8]}")
+    return status, t.as_dict()
+
+
+def restore_stream_device(index, store_blobs_dev: int, store_offsets, store_digests, out_dev: int, crypt=None,
+                          allow_bad: bool = False, window: int = 1 << 30, hip_stream: int = 0):
+    """The whole archive to out_dev through restore_range_device, in windows of about
+    ``window`` bytes that end on chunk boundaries (a chunk longer than the window is a window
+    of its own): this bounds the device scratch to a window's blobs and chunks.  A chunk is
+    decoded once per window that names it: dedup holds within a window, not across windows.
+    Returns (status per entry, list of the windows' timing dicts).  (A zero-length entry that
+    lies exactly on a window boundary belongs to no window and keeps BLOB_ST_NONE_REQUESTED.)"""
+    ends, digests = _index_arrays(index)
+    n = int(ends.size)
+    total = int(ends[-1]) if n else 0
+    status = np.full(n, BLOB_ST_NONE_REQUESTED, dtype=np.uint8)
+    timings = []
+    pos = 0
+    while pos < total:
+        # the last chunk end within the window, or the end of the chunk that holds `pos`
+        k = int(np.searchsorted(ends, pos + max(1, int(window)), side="right"))
+        end = int(ends[k - 1]) if k and int(ends[k - 1]) > pos else int(ends[np.searchsorted(ends, pos, side="right")])
+        st, t = restore_range_device((ends, digests), store_blobs_dev, store_offsets, store_digests, out_dev + pos,
+                                     pos, end - pos, crypt=crypt, allow_bad=allow_bad, hip_stream=hip_stream)
+        seen = st != BLOB_ST_NONE_REQUESTED
+        status[seen] = st[seen]
+        timings.append(t)
+        pos = end
+    return status, timings
 
 
 def index_stream_device(chunker: "Chunker", dev_ptr: int, length: int, key=None,

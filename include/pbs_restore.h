@@ -123,7 +123,10 @@ typedef struct {
  * its blob copied into scratch (pbs_copy_segments_device), loaded, opened, inflated and
  * verified ONCE (pbs_blob_decode_inflate_device with the index's chunk lengths and digests,
  * sizes_exact; a chunk of another length is BAD_SIZE for every kind, as CachedChunk::new
- * checks every chunk), and copied to the place of every entry that names it, clipped to the
+ * checks every chunk -- a longer one too: a blob that fails the digest in its entry's slot
+ * and whose entry is shorter than the index's longest chunk is decoded once more into a slot
+ * of that length, and is BAD_SIZE when its digest verifies there, as read_chunk verifies the
+ * whole chunk before its length is looked at), and copied to the place of every entry that names it, clipped to the
  * range (pbs_copy_segments_device).
  *
  * entry_status[i] (host, n): PBS_BLOB_ST_NONE_REQUESTED outside [i0, i1], else the status of

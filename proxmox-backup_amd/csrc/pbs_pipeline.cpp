@@ -46,6 +46,7 @@
 #include <mutex>
 #include <numeric>
 #include <memory>
+#include <set>
 #include <thread>
 #include <unordered_set>
 #include <vector>
@@ -56,6 +57,7 @@
 #include "dev_arena.h"
 #include "host_share.h"
 #include "pbs_digest.h"
+#include "pbs_fixed.h"
 #include "sha_host.h"
 
 namespace {
@@ -201,6 +203,11 @@ struct UploadExt {
     // pbs_upload_stream_host_crypt: the new chunks become encrypted blobs (44-byte headers)
     const pbs_crypt_config* crypt = nullptr;
     double encrypt_ms = 0;
+    // pbs_upload_fixed_host (include/pbs_fixed.h) with a dirty map: chunk i with dirty[i] == 0
+    // takes prev_digests[i], counts as known and is neither copied, hashed nor encoded
+    const uint8_t* dirty = nullptr;
+    const uint8_t* prev_digests = nullptr;
+    uint64_t dirty_chunks = 0, copied_bytes = 0;
 };
 
 // DataBlob::encode of `cnt` spans with the upload's crypt config, if any
@@ -221,9 +228,12 @@ int encode_upload_spans(const UploadExt& x, const uint8_t* d_data, size_t len, c
 int upload_stage(UploadExt& x, pbs::DevArena* area, const uint8_t* d_data, size_t len, const uint64_t* ends,
                  const uint8_t* digests, size_t n, hipStream_t st);
 
+// `fixed_chunk` != 0 (pbs_upload_fixed_host): the chunks are the grid of that size
+// (FixedChunkStream, pbs-client/src/chunk_stream.rs:80-134) instead of the chunker's cuts;
+// `avg` is then unused and no chunker is created or configured.
 int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, const uint8_t* key, size_t key_len,
                  int digest_cus, uint64_t* ends, uint8_t* digests, uint32_t* crcs, size_t cap, size_t* n_out,
-                 pbs_pipeline_timing* timing, UploadExt* ext) {
+                 pbs_pipeline_timing* timing, UploadExt* ext, uint64_t fixed_chunk = 0) {
     if (!n_out || (len && !host) || piece == 0 || (cap && (!ends || !digests)) ||
         key_len > PBS_DIGEST_MAX_KEY || (key_len && !key))
         return PBS_ERR_INVALID;
@@ -235,8 +245,13 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 16)
         return PBS_ERR_HIP;
     const int dig = std::min(std::max(digest_cus, 4), ncu - 8);
-    if (__builtin_popcountll(avg) != 1) return PBS_ERR_NOT_POW2;  // as pbs_chunker_new
-    if (cap < len / std::max<size_t>(avg >> 2, 65) + 3) return PBS_ERR_CAPACITY;  // pbs_chunker_cuts_bound
+    const uint8_t* const dirty = fixed_chunk && ext ? ext->dirty : nullptr;
+    if (fixed_chunk) {
+        if (cap < (len + fixed_chunk - 1) / fixed_chunk) return PBS_ERR_CAPACITY;
+    } else {
+        if (__builtin_popcountll(avg) != 1) return PBS_ERR_NOT_POW2;  // as pbs_chunker_new
+        if (cap < len / std::max<size_t>(avg >> 2, 65) + 3) return PBS_ERR_CAPACITY;  // pbs_chunker_cuts_bound
+    }
     const size_t npieces = (len + piece - 1) / piece;
     int rc = PBS_OK;
     auto hip_ok = [&](hipError_t e) {
@@ -251,7 +266,9 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
         const int& rc;
         ~Return() { pipe_release(a, rc == PBS_OK); }
     } give_back{A, rc};
-    if (!A->c || A->avg != avg) {
+    if (fixed_chunk) {
+        // the grid needs no chunker (one kept from an earlier stream stays as it is)
+    } else if (!A->c || A->avg != avg) {
         if (A->c) pbs_chunker_free(A->c);
         int err = PBS_OK;
         A->c = pbs_chunker_new(avg, &err);
@@ -260,7 +277,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     } else if (pbs::chunker_rewind(A->c) != PBS_OK) {
         return rc = PBS_ERR_HIP;
     }
-    pbs_chunker* const c = A->c;
+    pbs_chunker* const c = fixed_chunk ? nullptr : A->c;
     bool ok = true;
     if (A->dig != dig) {  // CU masks for this split
         A->drop_streams();
@@ -298,8 +315,8 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
             rc = PBS_ERR_NOMEM;
         }
     }
-    ok = ok && pbs_chunker_set_stream(c, s_scan) == PBS_OK &&
-         pbs_chunker_set_cu_count(c, ncu - dig) == PBS_OK;
+    ok = ok && (!c || (pbs_chunker_set_stream(c, s_scan) == PBS_OK &&
+                       pbs_chunker_set_cu_count(c, ncu - dig) == PBS_OK));
     if (!ok && rc == PBS_OK) rc = PBS_ERR_HIP;
     // the digest queue: control word + jobs in pinned coherent host memory (the GPU reads
     // them over PCIe), its claim counter and mirror in device memory
@@ -407,6 +424,20 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     std::vector<uint8_t> hmask;  // 1 = digest computed on the host
     std::vector<std::thread> hpool;
     hmask.assign(ok ? cap : 0, 0);
+    // dirty map: 1 = a clean chunk, whose digest is the previous one (neither GPU nor host)
+    std::vector<uint8_t> clean(ok ? cap : 0, 0);
+    // ... and the pieces that hold a byte of a dirty chunk: only they are copied
+    std::vector<uint8_t> piece_needed(npieces, 1);
+    if (dirty)
+        for (size_t k = 0; k < npieces; ++k) {
+            const uint64_t off = (uint64_t)k * piece, end = std::min<uint64_t>(off + piece, len);
+            uint8_t any = 0;
+            for (uint64_t i = off / fixed_chunk; i * fixed_chunk < end && !any; ++i) any = dirty[i] != 0;
+            piece_needed[k] = any;
+        }
+    uint64_t copied_bytes = 0;
+    for (size_t k = 0; k < npieces; ++k)
+        if (piece_needed[k]) copied_bytes += std::min<uint64_t>(piece, len - (uint64_t)k * piece);
     // the host threads' queue and zero-chunk memo (host_share.h); the upload path's encoder
     // waits per chunk for its digest: a host-routed chunk's flag there, a GPU job's `done` in
     // the job record; dig_final once every digest is in `digests`
@@ -422,8 +453,8 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
             const Clock::time_point tc = Clock::now();
             for (size_t k = 0; k < npieces; ++k) {
                 const size_t off = k * piece, n = std::min(piece, len - off);
-                if (hipMemcpyAsync(d_data + off, host + off, n, hipMemcpyHostToDevice, s_copy) !=
-                        hipSuccess ||
+                if ((piece_needed[k] &&
+                     hipMemcpyAsync(d_data + off, host + off, n, hipMemcpyHostToDevice, s_copy) != hipSuccess) ||
                     hipEventRecord(ev_copied[k], s_copy) != hipSuccess) {
                     copy_failed = true;
                     break;
@@ -525,7 +556,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
                         ext->enc_t.blocks += bt.blocks;
                         return r;
                     };
-                    const bool early = ext->n_known == 0;
+                    const bool early = ext->n_known == 0 && !dirty;  // (clean chunks are never encoded)
                     if (early) {
                         spans.resize(2 * m);
                         for (size_t k = 0; k < m; ++k) {
@@ -547,8 +578,9 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
                         if (spin % 64 == 63 && relaunch_due.load(std::memory_order_relaxed)) q_launch();
                         bool all = true;
                         for (size_t i = i0; i < i1 && all; ++i)
-                            all = hmask[i] ? hs.flag(i)
-                                           : __atomic_load_n(&q_jobs[jobof[i]].done, __ATOMIC_ACQUIRE) != 0;
+                            all = clean[i]   ? true
+                                  : hmask[i] ? hs.flag(i)
+                                             : __atomic_load_n(&q_jobs[jobof[i]].done, __ATOMIC_ACQUIRE) != 0;
                         if (all) break;
                         std::this_thread::sleep_for(std::chrono::microseconds(20));
                     }
@@ -564,8 +596,9 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
                     std::vector<uint64_t> fsp;
                     for (size_t i = i0; i < i1; ++i) {
                         std::array<uint8_t, 32> d;
-                        std::memcpy(d.data(), (fin || hmask[i]) ? digests + 32 * i : gdig.data() + 32 * (i - i0), 32);
-                        const bool kn = prev.count(d) || !seen.insert(d).second;
+                        std::memcpy(d.data(), (fin || hmask[i] || clean[i]) ? digests + 32 * i : gdig.data() + 32 * (i - i0), 32);
+                        // a clean chunk is known by the map; its digest joins no set
+                        const bool kn = clean[i] || prev.count(d) || !seen.insert(d).second;
                         ext->known_out[i] = kn ? 1 : 0;
                         if (!kn) {
                             fresh.push_back(i);
@@ -650,7 +683,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     uint64_t start = 0;  // start of the first chunk not yet digested
     // bytes of completed chunks per digest launch: a quarter of the stream, at most 16 GiB
     const uint64_t dbatch = std::max<uint64_t>(std::min<uint64_t>(len / 4, 16ull << 30), piece);
-    std::vector<uint64_t> tmp(ok ? pbs_chunker_cuts_bound(c, std::min(piece, len)) + 1 : 0);
+    std::vector<uint64_t> tmp(ok && c ? pbs_chunker_cuts_bound(c, std::min(piece, len)) + 1 : 0);
     std::vector<std::vector<uint64_t>> hb;  // host bounds/order stay alive until the end
     std::vector<std::vector<uint32_t>> ho;
     for (size_t k = 0; ok && rc == PBS_OK && k < npieces; ++k) {
@@ -663,13 +696,23 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
             break;
         }
         const size_t off = k * piece, pn = std::min(piece, len - off);
-        if (!hip_ok(hipStreamWaitEvent(s_scan, ev_copied[k], 0))) break;
         const Clock::time_point tk = Clock::now();
         size_t m = 0;
-        const int r = pbs_chunker_find_cuts_device(c, d_data + off, pn, k + 1 == npieces, tmp.data(),
-                                                   tmp.size(), &m);
+        int r = PBS_OK;
+        if (fixed_chunk) {
+            // the chunks this piece completes: the grid ends <= off + pn (`len` on the last
+            // piece), once the piece is resident -- the chunker's call waits for that too
+            if (!hip_ok(hipEventSynchronize(ev_copied[k]))) break;
+            for (uint64_t e; n + m < cap && (e = std::min<uint64_t>((uint64_t)(n + m + 1) * fixed_chunk, len)) <= off + pn;) {
+                ends[n + m++] = e;
+                if (e == len) break;
+            }
+        } else {
+            if (!hip_ok(hipStreamWaitEvent(s_scan, ev_copied[k], 0))) break;
+            r = pbs_chunker_find_cuts_device(c, d_data + off, pn, k + 1 == npieces, tmp.data(), tmp.size(), &m);
+        }
         chunk_ms += ms_since(tk);
-        if (dbg && ms_since(tk) > 20.0) {
+        if (c && dbg && ms_since(tk) > 20.0) {
             pbs_timing tt{};
             pbs_chunker_last_timing(c, &tt);
             std::fprintf(stderr, "piece %zu: find_cuts_device %.3f ms (at %.3f ms; scan %.3f fused %llu scan_pass %llu)\n",
@@ -686,7 +729,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
         }
         const size_t n0 = n;
         if (m) {
-            std::memcpy(ends + n, tmp.data(), m * 8);
+            if (!fixed_chunk) std::memcpy(ends + n, tmp.data(), m * 8);
             n += m;
         }
 
@@ -700,6 +743,11 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
             size_t nh = 0;
             for (size_t i = n0; i < n; ++i) {
                 const uint64_t s0 = i ? ends[i - 1] : 0, cl = ends[i] - s0;
+                if (dirty && !dirty[i]) {
+                    clean[i] = 1;
+                    std::memcpy(digests + 32 * i, ext->prev_digests + 32 * i, 32);
+                    continue;
+                }
                 const bool to_host = pbs::route_to_host(hthreads, host_min, now, cl, gpu_bpms, t_end);
                 if (to_host) {
                     hmask[i] = 1;
@@ -782,7 +830,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
         }
         gpu_done_at = ms_since(t0);
         if (rc == PBS_OK && n) {
-            if (hpool.empty()) {
+            if (hpool.empty() && !dirty) {
                 hip_ok(hipMemcpy(digests, d_dig, n * 32, hipMemcpyDeviceToHost));
             } else {  // the GPU's digests, merged around the host's
                 gdig.resize(n * 32);
@@ -791,7 +839,7 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
                     hpool.clear();
                     host_done_at = ms_since(t0);
                     for (size_t i = 0; i < n; ++i)
-                        if (!hmask[i]) std::memcpy(digests + 32 * i, gdig.data() + 32 * i, 32);
+                        if (!hmask[i] && !clean[i]) std::memcpy(digests + 32 * i, gdig.data() + 32 * i, 32);
                 }
             }
         }
@@ -827,7 +875,12 @@ int pipeline_run(size_t avg, const uint8_t* host, size_t len, size_t piece, cons
     up_finish();
     // the upload's part after the digests: known-chunk test and blobs, from the HBM copy
     // (on the copy stream: not CU-masked, idle since the last piece landed)
-    if (ext && rc == PBS_OK) rc = upload_stage(*ext, area, d_data, len, ends, digests, n, s_copy);
+    if (ext && rc == PBS_OK) {
+        ext->copied_bytes = copied_bytes;
+        ext->dirty_chunks = n;
+        for (size_t i = 0; i < n; ++i) ext->dirty_chunks -= clean[i];
+        rc = upload_stage(*ext, area, d_data, len, ends, digests, n, s_copy);
+    }
     const double total = ms_since(t0);
     if (timing) {
         timing->total_ms = total;
@@ -905,11 +958,29 @@ int upload_stage(UploadExt& x, pbs::DevArena* area, const uint8_t* d_data, size_
         (x.n_known && hipMemcpyAsync(d_kn, x.known, x.n_known * 32, hipMemcpyHostToDevice, st) != hipSuccess))
         return PBS_ERR_HIP;
     size_t reused = 0;
-    int rc = pbs_known_chunks_device(d_dig, n, x.n_known ? d_kn : nullptr, x.n_known, d_fl, &reused, st);
-    if (rc != PBS_OK) return rc;
-    if (hipMemcpyAsync(x.known_out, d_fl, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return PBS_ERR_HIP;
+    int rc = PBS_OK;
+    if (x.dirty) {
+        // with a dirty map the digests of clean chunks join no set (include/pbs_fixed.h): the
+        // client's HashSet (backup_writer.rs:690-697) over the hashed chunks, on the host
+        std::set<std::array<uint8_t, 32>> seen;
+        for (size_t q = 0; q < x.n_known; ++q) {
+            std::array<uint8_t, 32> d;
+            std::memcpy(d.data(), x.known + 32 * q, 32);
+            seen.insert(d);
+        }
+        for (size_t i = 0; i < n; ++i) {
+            std::array<uint8_t, 32> d;
+            std::memcpy(d.data(), digests + 32 * i, 32);
+            x.known_out[i] = !x.dirty[i] || !seen.insert(d).second ? 1 : 0;
+            reused += x.known_out[i];
+        }
+    } else {
+        rc = pbs_known_chunks_device(d_dig, n, x.n_known ? d_kn : nullptr, x.n_known, d_fl, &reused, st);
+        if (rc != PBS_OK) return rc;
+        if (hipMemcpyAsync(x.known_out, d_fl, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return PBS_ERR_HIP;
+    }
     const Clock::time_point t1 = Clock::now();
     // the new chunks as spans of the stream
     std::vector<uint64_t> spans;
@@ -1012,4 +1083,69 @@ extern "C" int pbs_upload_stream_host_crypt(size_t avg, const uint8_t* host, siz
     if (timing) timing->total_ms = ms_since(t0);
     if (encrypt_ms) *encrypt_ms = x.encrypt_ms;
     return rc;
+}
+
+// ---- the fixed twins (include/pbs_fixed.h): an image in chunks of chunk_size ----
+namespace {
+
+int upload_fixed(uint64_t chunk_size, const uint8_t* host, size_t len, size_t piece, const uint8_t* key,
+                 size_t key_len, const pbs_crypt_config* crypt, int digest_cus, const uint8_t* known, size_t n_known,
+                 int compress, const uint8_t* dirty, const uint8_t* prev_digests, uint64_t* ends, uint8_t* digests,
+                 uint8_t* is_known, size_t cap, size_t* n_out, uint8_t* blobs, size_t blobs_cap,
+                 uint64_t* blob_offsets, uint8_t* compressed, uint8_t index_csum[32], pbs_upload_fixed_timing* timing,
+                 double* encrypt_ms) {
+    if (timing) std::memset(timing, 0, sizeof(*timing));
+    if (encrypt_ms) *encrypt_ms = 0;
+    if (n_out) *n_out = 0;
+    if (__builtin_popcountll(chunk_size) != 1) return PBS_ERR_NOT_POW2;
+    if (chunk_size < 4096) return PBS_ERR_INVALID;
+    if (!is_known || !blob_offsets || (n_known && !known) || (blobs_cap && !blobs) || (dirty && !prev_digests))
+        return PBS_ERR_INVALID;
+    blob_offsets[0] = 0;
+    const Clock::time_point t0 = Clock::now();
+    pbs_upload_timing* const ut = timing ? &timing->up : nullptr;
+    UploadExt x{known, n_known, compress, is_known, blobs, blobs_cap, blob_offsets, compressed, ut};
+    x.crypt = crypt;
+    x.dirty = dirty;
+    x.prev_digests = prev_digests;
+    const int rc = pipeline_run(0, host, len, piece, key, key_len, digest_cus, ends, digests, nullptr, cap, n_out,
+                                ut ? &ut->pipe : nullptr, len ? &x : nullptr, chunk_size);
+    // the fixed branch of backup_writer.rs:685: the csum covers the digests alone
+    if (rc == PBS_OK && index_csum && n_out) pbs_sha256(digests, 32 * *n_out, index_csum);
+    if (timing) {
+        timing->up.total_ms = ms_since(t0);
+        timing->dirty_chunks = x.dirty_chunks;
+        timing->copied_bytes = x.copied_bytes;
+    }
+    if (encrypt_ms) *encrypt_ms = x.encrypt_ms;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int pbs_upload_fixed_host(uint64_t chunk_size, const uint8_t* host, size_t len, size_t piece,
+                                     const uint8_t* key, size_t key_len, int digest_cus, const uint8_t* known,
+                                     size_t n_known, int compress, const uint8_t* dirty,
+                                     const uint8_t* prev_digests, uint64_t* ends, uint8_t* digests,
+                                     uint8_t* is_known, size_t cap, size_t* n_out, uint8_t* blobs,
+                                     size_t blobs_cap, uint64_t* blob_offsets, uint8_t* compressed,
+                                     uint8_t index_csum[32], pbs_upload_fixed_timing* timing) {
+    return upload_fixed(chunk_size, host, len, piece, key, key_len, nullptr, digest_cus, known, n_known, compress,
+                        dirty, prev_digests, ends, digests, is_known, cap, n_out, blobs, blobs_cap, blob_offsets,
+                        compressed, index_csum, timing, nullptr);
+}
+
+extern "C" int pbs_upload_fixed_host_crypt(uint64_t chunk_size, const uint8_t* host, size_t len, size_t piece,
+                                           const pbs_crypt_config* crypt, int digest_cus, const uint8_t* known,
+                                           size_t n_known, int compress, const uint8_t* dirty,
+                                           const uint8_t* prev_digests, uint64_t* ends, uint8_t* digests,
+                                           uint8_t* is_known, size_t cap, size_t* n_out, uint8_t* blobs,
+                                           size_t blobs_cap, uint64_t* blob_offsets, uint8_t* compressed,
+                                           uint8_t index_csum[32], pbs_upload_fixed_timing* timing,
+                                           double* encrypt_ms) {
+    if (!crypt) return PBS_ERR_ARG;
+    // DataChunkBuilder::crypt_config: the digests are SHA-256(chunk || id_key)
+    return upload_fixed(chunk_size, host, len, piece, pbs_crypt_config_id_key(crypt), 32, crypt, digest_cus, known,
+                        n_known, compress, dirty, prev_digests, ends, digests, is_known, cap, n_out, blobs, blobs_cap,
+                        blob_offsets, compressed, index_csum, timing, encrypt_ms);
 }

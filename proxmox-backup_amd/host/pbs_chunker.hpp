@@ -39,6 +39,7 @@
 #include "pbs_blob.h"
 #include "pbs_digest.h"
 #include "pbs_restore.h"
+#include "pbs_fixed.h"
 
 namespace pbs {
 
@@ -619,6 +620,151 @@ class DynamicIndexReader {
     std::vector<uint64_t> ends_;
     std::vector<uint8_t> digests_;
     Digest csum_{};
+};
+
+// ---- the fixed-size chunk path (include/pbs_fixed.h) ----
+
+// FixedChunkStream (pbs-client/src/chunk_stream.rs:80-134): feed bytes in any pieces; chunks of
+// exactly chunk_size come out and, at the end, one last chunk of any non-zero length.
+class FixedChunkStream {
+  public:
+    explicit FixedChunkStream(size_t chunk_size) : chunk_size_(chunk_size) {
+        if (!chunk_size) throw std::invalid_argument("chunk_size must be positive");
+    }
+    // the chunks `data` completes
+    std::vector<std::vector<uint8_t>> feed(const uint8_t* data, size_t len) {
+        std::vector<std::vector<uint8_t>> out;
+        while (len) {
+            const size_t k = std::min(len, chunk_size_ - buf_.size());
+            buf_.insert(buf_.end(), data, data + k);
+            data += k;
+            len -= k;
+            if (buf_.size() == chunk_size_) {
+                out.push_back(std::move(buf_));
+                buf_.clear();
+            }
+        }
+        return out;
+    }
+    // the last, shorter chunk (:118-130); nothing after an exact multiple or an empty input
+    std::vector<std::vector<uint8_t>> finish() {
+        std::vector<std::vector<uint8_t>> out;
+        if (!buf_.empty()) out.push_back(std::move(buf_));
+        buf_.clear();
+        return out;
+    }
+
+  private:
+    size_t chunk_size_;
+    std::vector<uint8_t> buf_;
+};
+
+// FixedIndexReader (pbs-datastore/src/fixed_index.rs:59-215) over pbs_fidx_parse.
+class FixedIndexReader {
+  public:
+    FixedIndexReader(const uint8_t* image, size_t len) { parse(image, len); }
+    explicit FixedIndexReader(const std::string& path) {
+        std::FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) throw std::runtime_error("Unable to open fixed index " + path);
+        std::vector<uint8_t> image;
+        uint8_t buf[65536];
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) image.insert(image.end(), buf, buf + k);
+        std::fclose(f);
+        parse(image.data(), image.size());
+    }
+
+    std::array<uint8_t, 16> uuid{};
+    int64_t ctime = 0;
+    Digest index_csum{};
+    uint64_t size = 0;        // bytes of the archive
+    uint64_t chunk_size = 0;
+
+    size_t index_count() const { return digests_.size() / 32; }
+    uint64_t index_bytes() const { return size; }
+    std::optional<Digest> index_digest(size_t pos) const {
+        if (pos >= index_count()) return std::nullopt;
+        Digest d;
+        std::memcpy(d.data(), digests_.data() + 32 * pos, 32);
+        return d;
+    }
+    std::optional<ChunkReadInfo> chunk_info(size_t pos) const {
+        uint64_t s = 0, e = 0;
+        if (pbs_fidx_chunk_info(size, chunk_size, pos, &s, &e) != PBS_OK) return std::nullopt;
+        return ChunkReadInfo{s, e, *index_digest(pos)};
+    }
+    std::optional<std::pair<size_t, uint64_t>> chunk_from_offset(uint64_t offset) const {
+        size_t idx = 0;
+        uint64_t within = 0;
+        if (pbs_fidx_chunk_from_offset(size, chunk_size, offset, &idx, &within) != PBS_OK) return std::nullopt;
+        return std::make_pair(idx, within);
+    }
+    std::pair<Digest, uint64_t> compute_csum() const { return {csum_, size}; }
+    const std::vector<uint8_t>& digests() const { return digests_; }  // 32 bytes per entry
+
+  private:
+    void parse(const uint8_t* image, size_t len) {
+        const size_t cap = len > 4096 ? (len - 4096) / 32 : 0;
+        digests_.resize(32 * cap);
+        size_t n = 0;
+        const int rc = pbs_fidx_parse(image, len, uuid.data(), &ctime, index_csum.data(), csum_.data(), &size,
+                                      &chunk_size, digests_.data(), cap, &n);
+        if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_fidx_parse: ") + pbs_strerror(rc));
+        digests_.resize(32 * n);
+    }
+    std::vector<uint8_t> digests_;
+    Digest csum_{};
+};
+
+// FixedIndexWriter (fixed_index.rs:243-461) in memory: digests in any order (:394), close()
+// returns index_csum and image() the .fidx bytes.  A slot never written holds zeros.
+class FixedIndexWriter {
+  public:
+    FixedIndexWriter(uint64_t size, uint64_t chunk_size, const std::array<uint8_t, 16>& uuid, int64_t ctime)
+        : size_(size), chunk_size_(chunk_size), uuid_(uuid), ctime_(ctime) {
+        if (!chunk_size || (chunk_size & (chunk_size - 1))) throw std::invalid_argument("chunk_size: not a power of two");
+        if (!size) throw std::invalid_argument("invalid index size");
+        digests_.assign(32 * pbs_fidx_count(size, chunk_size), 0);
+    }
+    size_t index_length() const { return digests_.size() / 32; }
+    size_t check_chunk_alignment(uint64_t end_offset, uint64_t chunk_len) const {
+        size_t idx = 0;
+        if (pbs_fidx_check_chunk_alignment(size_, chunk_size_, end_offset, chunk_len, &idx) != PBS_OK)
+            throw std::runtime_error("chunk with unexpected offset or length");
+        return idx;
+    }
+    void add_digest(size_t index, const Digest& digest) {
+        if (index >= index_length()) throw std::out_of_range("add digest failed - index out of range");
+        if (closed_) throw std::runtime_error("cannot write to closed index file.");
+        std::memcpy(digests_.data() + 32 * index, digest.data(), 32);
+    }
+    void add_chunk(uint64_t end_offset, uint64_t chunk_len, const Digest& digest) {
+        add_digest(check_chunk_alignment(end_offset, chunk_len), digest);
+    }
+    void clone_data_from(const FixedIndexReader& reader) {
+        if (index_length() != reader.index_count()) throw std::runtime_error("clone_data_from failed - index sizes not equal");
+        for (size_t i = 0; i < index_length(); ++i) add_digest(i, *reader.index_digest(i));
+    }
+    Digest close() {
+        if (closed_) throw std::runtime_error("cannot close already closed index file.");
+        closed_ = true;
+        image_.resize(pbs_fidx_size(index_length()));
+        Digest csum{};
+        const int rc = pbs_fidx_build(digests_.data(), size_, chunk_size_, uuid_.data(), ctime_, image_.data(),
+                                      image_.size(), csum.data());
+        if (rc != PBS_OK) throw std::runtime_error(std::string("pbs_fidx_build: ") + pbs_strerror(rc));
+        return csum;
+    }
+    const std::vector<uint8_t>& image() const {
+        if (!closed_) throw std::runtime_error("the index is not closed yet");
+        return image_;
+    }
+
+  private:
+    uint64_t size_, chunk_size_;
+    std::array<uint8_t, 16> uuid_;
+    int64_t ctime_;
+    std::vector<uint8_t> digests_, image_;
+    bool closed_ = false;
 };
 
 }  // namespace pbs

@@ -78,6 +78,11 @@ EXPORTED_SYMBOLS = (
     # restoring a .didx stream (include/pbs_restore.h)
     "pbs_didx_count", "pbs_didx_parse", "pbs_didx_chunk_from_offset", "pbs_digest_lookup_device",
     "pbs_digest_lookup_host", "pbs_copy_segments_device", "pbs_restore_range_device", "pbs_restore_release",
+    # the fixed-size chunk path (include/pbs_fixed.h)
+    "pbs_fidx_count", "pbs_fidx_size", "pbs_fidx_build", "pbs_fidx_parse", "pbs_fidx_chunk_info",
+    "pbs_fidx_chunk_from_offset", "pbs_fidx_check_chunk_alignment", "pbs_fixed_dirty_device", "pbs_fixed_dirty_host",
+    "pbs_fixed_digests_device", "pbs_upload_fixed_host", "pbs_upload_fixed_host_crypt",
+    "pbs_restore_fixed_range_device",
 )
 
 
@@ -201,6 +206,24 @@ class UploadTiming(ctypes.Structure):
                 for k, _ in self._fields_}
 
 
+class FixedDigestTiming(ctypes.Structure):
+    _fields_ = [("total_ms", ctypes.c_double), ("gpu_ms", ctypes.c_double),
+                ("hashed_chunks", ctypes.c_uint64), ("hashed_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class UploadFixedTiming(ctypes.Structure):
+    _fields_ = [("up", UploadTiming), ("dirty_chunks", ctypes.c_uint64), ("copied_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = self.up.as_dict()
+        d["dirty_chunks"] = self.dirty_chunks
+        d["copied_bytes"] = self.copied_bytes
+        return d
+
+
 class HybridOpts(ctypes.Structure):
     _fields_ = [
         ("host_threads", ctypes.c_int), ("host_min_len", ctypes.c_uint64),
@@ -318,6 +341,24 @@ def lib():
         "pbs_copy_segments_device": ([p, p, p, p, p, sz, p], i),
         "pbs_restore_range_device": ([p, p, sz, p, p, p, sz, p, u64, u64, p, p, ctypes.POINTER(RestoreTiming), p], i),
         "pbs_restore_release": ([], None),
+        "pbs_fidx_count": ([u64, u64], sz),
+        "pbs_fidx_size": ([sz], sz),
+        "pbs_fidx_build": ([p, u64, u64, p, ctypes.c_int64, p, sz, p], i),
+        "pbs_fidx_parse": ([p, sz, p, ctypes.POINTER(ctypes.c_int64), p, p, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                            p, sz, ctypes.POINTER(sz)], i),
+        "pbs_fidx_chunk_info": ([u64, u64, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)], i),
+        "pbs_fidx_chunk_from_offset": ([u64, u64, u64, ctypes.POINTER(sz), ctypes.POINTER(u64)], i),
+        "pbs_fidx_check_chunk_alignment": ([u64, u64, u64, u64, ctypes.POINTER(sz)], i),
+        "pbs_fixed_dirty_device": ([p, p, u64, u64, p, ctypes.POINTER(sz), p], i),
+        "pbs_fixed_dirty_host": ([p, p, u64, u64, p, ctypes.POINTER(sz)], i),
+        "pbs_fixed_digests_device": ([p, u64, u64, p, sz, p, p, p, p, ctypes.POINTER(FixedDigestTiming), p], i),
+        "pbs_upload_fixed_host": ([u64, p, sz, sz, p, sz, i, p, sz, i, p, p, p, p, p, sz, ctypes.POINTER(sz),
+                                   p, sz, p, p, p, ctypes.POINTER(UploadFixedTiming)], i),
+        "pbs_upload_fixed_host_crypt": ([u64, p, sz, sz, p, i, p, sz, i, p, p, p, p, p, sz, ctypes.POINTER(sz),
+                                         p, sz, p, p, p, ctypes.POINTER(UploadFixedTiming),
+                                         ctypes.POINTER(ctypes.c_double)], i),
+        "pbs_restore_fixed_range_device": ([p, sz, u64, u64, p, p, p, sz, p, u64, u64, p, p,
+                                            ctypes.POINTER(RestoreTiming), p], i),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
@@ -1557,3 +1598,382 @@ def pipeline_host(data, avg: int, piece: int = 1 << 30, key=None, digest_cus: in
     if crc:
         return ends[: n.value].copy(), dig[: n.value].copy(), crcs[: n.value].copy(), t.as_dict()
     return ends[: n.value].copy(), dig[: n.value].copy(), t.as_dict()
+
+
+# ---- the fixed-size chunk path: .fidx archives, VM images (include/pbs_fixed.h) ----
+FIDX_MAGIC = bytes([47, 127, 65, 237, 145, 253, 15, 205])  # file_formats.rs:20-21
+FIDX_HEADER = 4096
+
+
+class FixedChunkStream:
+    """chunk_stream.rs:80-134: feed bytes in any pieces; chunks of exactly ``chunk_size`` come
+    out and, at the end, one last chunk of any non-zero length (:106-133).  ``feed(data)``
+    returns the chunks completed by it, ``finish()`` the last partial chunk in a list (empty
+    when the input was a multiple of the chunk size or empty); ``chunks(pieces)`` does both
+    over an iterable."""
+
+    def __init__(self, chunk_size: int):
+        if chunk_size <= 0:
+            raise ValueError("chunk_size must be positive")
+        self.chunk_size = int(chunk_size)
+        self._buf = bytearray()
+
+    def feed(self, data) -> list:
+        self._buf += bytes(data)
+        c, out = self.chunk_size, []
+        k = len(self._buf) // c
+        for j in range(k):
+            out.append(bytes(self._buf[j * c:(j + 1) * c]))
+        del self._buf[:k * c]
+        return out
+
+    def finish(self) -> list:
+        out = [bytes(self._buf)] if self._buf else []
+        self._buf = bytearray()
+        return out
+
+    def chunks(self, pieces: Iterable) -> Iterator[bytes]:
+        for piece in pieces:
+            yield from self.feed(piece)
+        yield from self.finish()
+
+
+def fidx_count(size: int, chunk_size: int) -> int:
+    return int(lib().pbs_fidx_count(int(size), int(chunk_size)))
+
+
+def fidx_size(n: int) -> int:
+    return int(lib().pbs_fidx_size(int(n)))
+
+
+def fidx_build(digests, size: int, chunk_size: int, uuid: bytes = bytes(16), ctime: int = 0):
+    """pbs_fidx_build: the .fidx image (bytes) and index_csum of an archive of ``size`` bytes in
+    chunks of ``chunk_size`` with the ceil(size / chunk_size) 32-byte ``digests``
+    (fixed_index.rs:20-32 header, :341-362 csum)."""
+    d = _digest_rows(digests)
+    if chunk_size <= 0:
+        raise ChunkerError(PBS_ERR_INVALID, "pbs_fidx_build")
+    n = fidx_count(size, chunk_size)
+    if d.shape[0] != n:
+        raise ValueError(f"{d.shape[0]} digests, the archive has {n} chunks")
+    if len(uuid) != 16:
+        raise ValueError("uuid must be 16 bytes")
+    cap = fidx_size(n)
+    out = np.empty(cap, dtype=np.uint8)
+    csum = (ctypes.c_uint8 * 32)()
+    ub = ctypes.create_string_buffer(bytes(uuid), 16)
+    rc = lib().pbs_fidx_build(d.ctypes.data if n else None, int(size), int(chunk_size), ub, int(ctime),
+                              out.ctypes.data, cap, csum)
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fidx_build")
+    return out.tobytes(), bytes(csum)
+
+
+def fidx_parse(image, cap: Optional[int] = None):
+    """pbs_fidx_parse: (uuid, ctime, header_csum, computed_csum, size, chunk_size, digests (n, 32)).
+    Raises ChunkerError with the call's code (``.n`` = the image's entry count where the call
+    set it) where FixedIndexReader::new bails, for a chunk size that is no power of two
+    (PBS_ERR_NOT_POW2) and when ``cap`` (default: what the image's length holds) is too small."""
+    a = _as_u8(image)
+    if cap is None:
+        cap = max(0, (a.size - FIDX_HEADER) // 32)
+    digests = np.zeros((cap, 32), dtype=np.uint8)
+    uuid, hc, cc = (ctypes.c_uint8 * 16)(), (ctypes.c_uint8 * 32)(), (ctypes.c_uint8 * 32)()
+    ctime, n = ctypes.c_int64(0), ctypes.c_size_t(0)
+    size, cs = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().pbs_fidx_parse(_ptr(a), a.size, uuid, ctypes.byref(ctime), hc, cc, ctypes.byref(size), ctypes.byref(cs),
+                              digests.ctypes.data if cap else None, cap, ctypes.byref(n))
+    if rc != PBS_OK:
+        err = ChunkerError(rc, "pbs_fidx_parse")
+        err.n = int(n.value)
+        raise err
+    return bytes(uuid), int(ctime.value), bytes(hc), bytes(cc), int(size.value), int(cs.value), digests[:n.value]
+
+
+def fidx_chunk_info(size: int, chunk_size: int, pos: int):
+    """pbs_fidx_chunk_info: (start, end) of chunk ``pos`` (the last one clipped), None past the end."""
+    if pos < 0:
+        return None
+    s, e = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().pbs_fidx_chunk_info(int(size), int(chunk_size), int(pos), ctypes.byref(s), ctypes.byref(e))
+    return (int(s.value), int(e.value)) if rc == PBS_OK else None
+
+
+def fidx_chunk_from_offset(size: int, chunk_size: int, offset: int):
+    """pbs_fidx_chunk_from_offset: (chunk, offset inside it), or None at or past ``size``."""
+    idx, within = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    rc = lib().pbs_fidx_chunk_from_offset(int(size), int(chunk_size), int(offset), ctypes.byref(idx),
+                                          ctypes.byref(within))
+    if rc == PBS_ERR_INVALID and chunk_size:
+        return None
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fidx_chunk_from_offset")
+    return int(idx.value), int(within.value)
+
+
+def fidx_check_chunk_alignment(size: int, chunk_size: int, end_offset: int, chunk_len: int) -> int:
+    """pbs_fidx_check_chunk_alignment (fixed_index.rs:364-392): the chunk's index; ChunkerError
+    where the reference bails."""
+    idx = ctypes.c_size_t(0)
+    rc = lib().pbs_fidx_check_chunk_alignment(int(size), int(chunk_size), int(end_offset), int(chunk_len),
+                                              ctypes.byref(idx))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fidx_check_chunk_alignment")
+    return int(idx.value)
+
+
+class FixedIndexReader:
+    """fixed_index.rs:59-215 over the C reader: built from the bytes of a .fidx image or from a
+    path.  ``index_csum`` is the header's checksum and ``compute_csum()`` the one over the
+    digests; as in the reference, opening does not compare them.  Raises ChunkerError where the
+    reference's ``new`` bails, and for a chunk size that is no power of two."""
+
+    def __init__(self, source):
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as f:
+                source = f.read()
+        (self.uuid, self.ctime, self.index_csum, self._csum, self.size, self.chunk_size,
+         self.digests) = fidx_parse(bytes(source))
+
+    def index_count(self) -> int:
+        return int(self.digests.shape[0])
+
+    def index_bytes(self) -> int:
+        return self.size
+
+    def index_digest(self, pos: int) -> Optional[bytes]:
+        return self.digests[pos].tobytes() if 0 <= pos < self.index_count() else None
+
+    def chunk_info(self, pos: int):
+        """(start, end, digest) of entry ``pos``, or None past the end."""
+        r = fidx_chunk_info(self.size, self.chunk_size, pos)
+        return None if r is None else (r[0], r[1], self.digests[pos].tobytes())
+
+    def chunk_from_offset(self, offset: int):
+        return fidx_chunk_from_offset(self.size, self.chunk_size, offset)
+
+    def compute_csum(self):
+        """(checksum over the digests, the archive's length)."""
+        return self._csum, self.size
+
+    def ends(self) -> np.ndarray:
+        """The chunk END offsets, the last one clipped to the size."""
+        n = self.index_count()
+        return np.minimum((np.arange(n, dtype=np.uint64) + 1) * np.uint64(self.chunk_size), np.uint64(self.size))
+
+
+class FixedIndexWriter:
+    """fixed_index.rs:243-461 in memory: digests may come in any order (:394); ``close()``
+    returns index_csum and ``image()`` the .fidx bytes (``close(path)`` also writes them: tmp
+    file + rename).  A slot never written holds zeros, as the reference's fresh mapping does."""
+
+    def __init__(self, size: int, chunk_size: int, uuid: Optional[bytes] = None, ctime: Optional[int] = None):
+        import time
+
+        if chunk_size <= 0 or chunk_size & (chunk_size - 1):
+            raise ChunkerError(PBS_ERR_NOT_POW2 if chunk_size > 0 else PBS_ERR_INVALID, "FixedIndexWriter")
+        if size <= 0:
+            raise ChunkerError(PBS_ERR_INVALID, "FixedIndexWriter: invalid index size")  # :295-296
+        self.size, self.chunk_size = int(size), int(chunk_size)
+        self.uuid = bytes(uuid) if uuid is not None else os.urandom(16)
+        self.ctime = int(time.time()) if ctime is None else int(ctime)
+        self.index_length = fidx_count(size, chunk_size)
+        self._digests = np.zeros((self.index_length, 32), dtype=np.uint8)
+        self._image = None
+        self.closed = False
+
+    def check_chunk_alignment(self, end_offset: int, chunk_len: int) -> int:
+        return fidx_check_chunk_alignment(self.size, self.chunk_size, end_offset, chunk_len)
+
+    def add_digest(self, index: int, digest: bytes):
+        if not 0 <= index < self.index_length:
+            raise IndexError(f"add digest failed - index out of range ({index} >= {self.index_length})")
+        if self.closed:
+            raise RuntimeError("cannot write to closed index file.")
+        if len(digest) != 32:
+            raise ValueError("digest must be 32 bytes")
+        self._digests[index] = np.frombuffer(bytes(digest), dtype=np.uint8)
+
+    def add_chunk(self, end_offset: int, chunk_len: int, digest: bytes) -> int:
+        idx = self.check_chunk_alignment(end_offset, chunk_len)
+        self.add_digest(idx, digest)
+        return idx
+
+    def clone_data_from(self, reader: "FixedIndexReader"):
+        if self.index_length != reader.index_count():
+            raise ValueError("clone_data_from failed - index sizes not equal")
+        for k in range(self.index_length):
+            self.add_digest(k, reader.index_digest(k))
+
+    def close(self, path: Optional[str] = None) -> bytes:
+        if self.closed:
+            raise RuntimeError("cannot close already closed index file.")
+        self.closed = True
+        self._image, csum = fidx_build(self._digests, self.size, self.chunk_size, self.uuid, self.ctime)
+        if path is not None:
+            tmp = os.path.splitext(path)[0] + ".tmp_fidx"
+            with open(tmp, "wb") as f:
+                f.write(self._image)
+            os.replace(tmp, path)
+        return csum
+
+    def image(self) -> bytes:
+        if self._image is None:
+            raise RuntimeError("the index is not closed yet")
+        return self._image
+
+
+def fixed_dirty_host(prev, cur, chunk_size: int):
+    """pbs_fixed_dirty_host: (flags (n uint8, 1 = some byte of the chunk differs), n_dirty) of two
+    host images of equal length, by memcmp per chunk."""
+    a, b = _as_u8(prev), _as_u8(cur)
+    if a.size != b.size:
+        raise ValueError("the images differ in length")
+    n = fidx_count(a.size, chunk_size) if chunk_size > 0 else 0
+    flags = np.zeros(n, dtype=np.uint8)
+    cnt = ctypes.c_size_t(0)
+    rc = lib().pbs_fixed_dirty_host(_ptr(a), _ptr(b), a.size, int(chunk_size), _ptr(flags), ctypes.byref(cnt))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fixed_dirty_host")
+    return flags, int(cnt.value)
+
+
+def fixed_dirty_device(prev_dev: int, cur_dev: int, size: int, chunk_size: int, dirty_dev: int,
+                       hip_stream: int = 0) -> int:
+    """pbs_fixed_dirty_device: writes the n = ceil(size / chunk_size) flags to device address
+    dirty_dev and returns n_dirty.  Both images are device addresses of any alignment."""
+    cnt = ctypes.c_size_t(0)
+    rc = lib().pbs_fixed_dirty_device(ctypes.c_void_p(prev_dev or None), ctypes.c_void_p(cur_dev or None), int(size),
+                                      int(chunk_size), ctypes.c_void_p(dirty_dev or None), ctypes.byref(cnt),
+                                      ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fixed_dirty_device")
+    return int(cnt.value)
+
+
+def _dirty_args(dirty, prev_digests, n: int):
+    if dirty is None:
+        return None, None
+    d = np.ascontiguousarray(np.asarray(dirty, dtype=np.uint8).reshape(-1))
+    if d.size != n:
+        raise ValueError(f"the dirty map holds {d.size} flags, the image has {n} chunks")
+    if prev_digests is None:
+        return d, None
+    pd = _digest_rows(prev_digests)
+    if pd.shape[0] != n:
+        raise ValueError(f"{pd.shape[0]} previous digests, the image has {n} chunks")
+    return d, pd
+
+
+def fixed_digests_device(dev_ptr: int, size: int, chunk_size: int, key=None, dirty=None, prev_digests=None,
+                         hip_stream: int = 0):
+    """pbs_fixed_digests_device: ((n, 32) digests, index_csum, timing dict) of the image at
+    device address dev_ptr.  With ``dirty`` (n flags) the clean chunks take ``prev_digests``
+    verbatim and are not read."""
+    n = fidx_count(size, chunk_size) if chunk_size > 0 else 0
+    d, pd = _dirty_args(dirty, prev_digests, n)
+    dig = np.zeros((n, 32), dtype=np.uint8)
+    csum = (ctypes.c_uint8 * 32)()
+    kb, kl = _key_arg(key)
+    t = FixedDigestTiming()
+    rc = lib().pbs_fixed_digests_device(ctypes.c_void_p(dev_ptr or None), int(size), int(chunk_size), kb, kl,
+                                        d.ctypes.data if d is not None else None,
+                                        pd.ctypes.data if pd is not None else None, _ptr(dig), csum, ctypes.byref(t),
+                                        ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_fixed_digests_device")
+    return dig, bytes(csum), t.as_dict()
+
+
+def upload_fixed_host(data, chunk_size: int, known=None, key=None, piece: int = 1 << 30, dirty=None,
+                      prev_digests=None, uuid: bytes = bytes(16), ctime: int = 0, compress: bool = True,
+                      digest_cus: int = 64, blobs_out=None, crypt=None) -> dict:
+    """The client's upload of one fixed-index image (``prefix == "fixed"``,
+    backup_writer.rs:272-275) from a host buffer: upload_stream_host over the grid of
+    ``chunk_size`` (FixedChunkStream) instead of the chunker's cuts; the same dict, with the
+    .fidx image under ``fidx`` and ``csum`` = SHA-256 over the digests alone (:685).
+    ``dirty`` (n flags) with ``prev_digests`` (n, 32): a clean chunk takes its previous digest,
+    is known, has an empty blob and is neither copied, hashed nor encoded; timing gains
+    ``dirty_chunks`` and ``copied_bytes``.  The digests of clean chunks take part in the known
+    test only where ``known`` lists them."""
+    a = _as_u8(data)
+    cap = (fidx_count(a.size, chunk_size) if chunk_size > 0 else 0) + 1
+    d, pd = _dirty_args(dirty, prev_digests, cap - 1)
+    ends = np.empty(cap, dtype=np.uint64)
+    dig = np.empty((cap, 32), dtype=np.uint8)
+    is_known = np.empty(cap, dtype=np.uint8)
+    offs = np.zeros(cap + 1, dtype=np.uint64)
+    comp = np.empty(cap, dtype=np.uint8)
+    if crypt is not None and key is not None:
+        raise ValueError("crypt brings its own digest key (id_key)")
+    bcap = (BLOB_ENC_HEADER_SIZE if crypt is not None else BLOB_HEADER_SIZE) * cap + a.size
+    blobs = blobs_out if blobs_out is not None else np.empty(max(bcap, 1), dtype=np.uint8)
+    if blobs.size < bcap:
+        raise ValueError(f"blobs_out holds {blobs.size} bytes, the image needs up to {bcap}")
+    kd = np.zeros((0, 32), dtype=np.uint8)
+    if known is not None and len(known):
+        kd = np.frombuffer(b"".join(sorted(bytes(x) for x in known)), dtype=np.uint8).reshape(-1, 32)
+    kb, kl = _key_arg(key)
+    n = ctypes.c_size_t(0)
+    t = UploadFixedTiming()
+    enc_ms = ctypes.c_double(0.0)
+    csum = (ctypes.c_uint8 * 32)()
+    dp = d.ctypes.data if d is not None else None
+    pp = pd.ctypes.data if pd is not None else None
+    tail = (1 if compress else 0, dp, pp, ends.ctypes.data, dig.ctypes.data, is_known.ctypes.data, cap,
+            ctypes.byref(n), blobs.ctypes.data, blobs.size, offs.ctypes.data, comp.ctypes.data, csum, ctypes.byref(t))
+    if crypt is not None:
+        rc = lib().pbs_upload_fixed_host_crypt(int(chunk_size), _ptr(a), a.size, piece, crypt.handle, digest_cus,
+                                               kd.ctypes.data if kd.size else None, kd.shape[0], *tail,
+                                               ctypes.byref(enc_ms))
+    else:
+        rc = lib().pbs_upload_fixed_host(int(chunk_size), _ptr(a), a.size, piece, kb, kl, digest_cus,
+                                         kd.ctypes.data if kd.size else None, kd.shape[0], *tail)
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_upload_fixed_host_crypt" if crypt is not None else "pbs_upload_fixed_host")
+    m = n.value
+    ends, dig, is_known, offs, comp = ends[:m].copy(), dig[:m].copy(), is_known[:m].copy(), offs[:m + 1].copy(), comp[:m].copy()
+    image = fidx_build(dig, a.size, chunk_size, uuid, ctime)[0] if m else b""
+    starts = np.concatenate([[0], ends[:-1]]).astype(np.uint64) if m else np.zeros(0, np.uint64)
+    new = [(int(starts[k]), int(ends[k] - starts[k])) for k in np.flatnonzero(is_known == 0)]
+    td = t.as_dict()
+    if crypt is not None:
+        td["encrypt_ms"] = enc_ms.value
+    stats = {k: td[k] for k in ("chunk_count", "chunk_reused", "size", "size_reused", "size_compressed")}
+    return {"ends": ends, "digests": dig, "known": is_known, "csum": bytes(csum), "fidx": image,
+            "blobs": blobs[:int(offs[-1])] if m else blobs[:0], "blob_offsets": offs, "compressed": comp,
+            "new_chunks": new, "stats": stats, "timing": td}
+
+
+def restore_fixed_range_device(reader, store_blobs_dev: int, store_offsets, store_digests, out_dev: int,
+                               offset: int = 0, length: Optional[int] = None, crypt=None, allow_bad: bool = False,
+                               hip_stream: int = 0):
+    """pbs_restore_fixed_range_device: image bytes [offset, offset + length) of the archive that
+    ``reader`` (a FixedIndexReader, or (digests, size, chunk_size)) describes, to device address
+    out_dev; store, result and errors as restore_range_device."""
+    if isinstance(reader, FixedIndexReader):
+        digests, size, chunk_size = reader.digests, reader.size, reader.chunk_size
+    else:
+        digests, size, chunk_size = reader
+    digests = _digest_rows(digests)
+    n = int(digests.shape[0])
+    so = np.ascontiguousarray(np.asarray(store_offsets, dtype=np.uint64))
+    sd = _digest_rows(store_digests)
+    m = int(sd.shape[0])
+    if so.size != m + 1:
+        raise ValueError(f"store_offsets holds {so.size} values, {m} blobs need {m + 1}")
+    if length is None:
+        length = max(0, int(size) - int(offset))
+    status = np.full(n, BLOB_ST_NONE_REQUESTED, dtype=np.uint8)
+    t = RestoreTiming()
+    rc = lib().pbs_restore_fixed_range_device(
+        digests.ctypes.data if n else None, n, int(size), int(chunk_size), ctypes.c_void_p(store_blobs_dev or None),
+        so.ctypes.data, sd.ctypes.data if m else None, m, crypt.handle if crypt is not None else None, int(offset),
+        int(length), ctypes.c_void_p(out_dev or None), status.ctypes.data if n else None, ctypes.byref(t),
+        ctypes.c_void_p(hip_stream))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_restore_fixed_range_device")
+    if t.failed and not allow_bad:
+        bad = [(int(k), int(status[k])) for k in np.flatnonzero((status != BLOB_ST_OK) & (status != BLOB_ST_NONE_REQUESTED))]
+        raise ChunkerError(PBS_ERR_INVALID, f"restore: {t.failed} entries failed (entry, status): {bad[:8]}")
+    return status, t.as_dict()

@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "aes_gcm.h"
+#include "dev_copy.h"
 #include "pbs_blob.h"
 
 namespace pbs {
@@ -53,7 +54,7 @@ namespace gcm {
 // the config's key record on device `dev`, copied there on first use (pbs_crypt.hip)
 KeyDev* device_key(const pbs_crypt_config* cc, int dev);
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// (u32x4: dev_copy.h) a 16-byte block of a payload, at any address, as the GCM kernels load and store it
 typedef u32x4 u32x4_u __attribute__((aligned(1)));
 
 __host__ __device__ __forceinline__ B128 words_to_b128(uint4 w) {

@@ -3,7 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <vector>
+
+#include "pbs_chunker.h"
 
 typedef struct pbs_chunker pbs_chunker;            // include/pbs_chunker.h
 typedef struct pbs_crypt_config pbs_crypt_config;  // include/pbs_blob.h
@@ -326,6 +329,48 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// The device of the stream a call was handed and its CU count: with DeviceGuard, the prelude
+// of every read-path call.
+struct StreamDevice {
+    int dev = 0, ncu = 0;
+    bool ok = false;
+    explicit StreamDevice(hipStream_t st) {
+        ok = hipStreamGetDevice(st, &dev) == hipSuccess &&
+             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
+    }
+};
+
+// Host milliseconds since `t0`, for the total_ms of the timing records (pbs_digest.hip keeps
+// a two-argument hms of its own for its intervals).
+using HClock = std::chrono::steady_clock;
+inline double hms(HClock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(HClock::now() - t0).count();
+}
+
+// The return code of a call made of many steps: the first failure stays.  fail takes a PBS_*
+// code (PBS_OK, the code of a step that went well, changes nothing), ok a HIP one; both return
+// whether the call is still good, so steps chain with && and stop at the first failure.
+struct CallRc {
+    int rc = PBS_OK;
+    bool fail(int r) {
+        if (rc == PBS_OK) rc = r;
+        return rc == PBS_OK;
+    }
+    bool ok(hipError_t e) { return fail(e == hipSuccess ? PBS_OK : PBS_ERR_HIP); }
+};
+
+// pbs_decode.hip: the order in which a read call hashes its blobs' contents.  Blob i is chunk
+// stride * i of the call's bounds list (host copy `bounds`; stride 1: the packed output's
+// offsets, stride 2: [slot start, content end, next slot start, ...]) and cls[i] says how it
+// is hashed: 0 not at all, 1 plain, 2 with the config's id_key.  Fills `ord` with the chunk
+// numbers, plain first, keyed second, longest first within each (stable), and returns the
+// number of plain ones.
+size_t digest_order(const uint8_t* cls, const uint64_t* bounds, uint32_t stride, size_t n, std::vector<uint32_t>& ord);
+// The one or two pbs_digest_chunks_async calls for such an order (device copies of the
+// bounds and of `nord` order entries): digest of chunk c to dig_dev + 32 c.
+int digest_in_order(const uint8_t* data_dev, uint64_t data_len, const uint64_t* bounds_dev, const uint32_t* ord_dev,
+                    size_t nplain, size_t nord, const pbs_crypt_config* cfg, uint8_t* dig_dev, hipStream_t st);
 
 // pbs_blob.hip: free the blob-CRC chunk counter kept for `st` (call before destroying it)
 void release_stream_counter(hipStream_t st);

@@ -11,8 +11,8 @@
 //     lengths go through the in-house scan to the output offsets, which the host reads
 //     (it needs them for the item lists, as the encoder needs its blob offsets).
 //  2. the CRC kernel of pbs_blob.hip over the spans (launch_crc32_spans).
-//  3. copy_kernel, one workgroup per 64 KiB piece of an unencrypted payload, into the
-//     packed output.
+//  3. segment_copy_kernel (dev_copy.h), one workgroup per 64 KiB piece of an unencrypted
+//     payload, into the packed output; the host builds its items from the offsets it read.
 //  4. gcm_open_prepare_kernel, one lane per encrypted blob: J0 from the header's IV through
 //     GHASH and AES_K(J0); gcm_open_kernel, the sibling of gcm_ctr_ghash_kernel
 //     (pbs_crypt.hip: the same 256 lanes, 64 KiB segments counted from the payload's end,
@@ -33,12 +33,12 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
 #include "aes_gcm.h"
 #include "dev_arena.h"
+#include "dev_copy.h"
 #include "gcm_dev.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
@@ -55,7 +55,6 @@ constexpr int kThreads = kGcmThreads;
 constexpr int kRows = kGcmRows;
 constexpr uint32_t kSegBlocks = kGcmSegBlocks;
 constexpr int kGroupsPerCu = kGcmGroupsPerCu;
-constexpr uint32_t kPiece = PBS_GCM_SEGMENT_BYTES;  // bytes one workgroup copies
 
 // file_formats.rs:9-18
 __device__ __constant__ uint8_t kMagicsDev[4][8] = {{66, 171, 56, 7, 190, 131, 112, 161},
@@ -133,28 +132,6 @@ __global__ void classify_kernel(const uint8_t* __restrict__ blobs, const uint64_
     spans[2 * i] = f ? b1 : b0 + h;
     spans[2 * i + 1] = b1;
     order[i] = (uint32_t)(2 * i);
-}
-
-// item = blob << 32 | piece: the piece's bytes of an unencrypted payload into the packed output.
-// Source and destination have different residues mod 16: both sides move as unaligned
-// 16-byte accesses, the piece's last bytes one by one.
-__global__ __launch_bounds__(kThreads) void copy_kernel(const uint8_t* __restrict__ blobs,
-                                                        const uint64_t* __restrict__ items, uint64_t nitems,
-                                                        const uint64_t* __restrict__ spans,
-                                                        const uint64_t* __restrict__ ooff,
-                                                        uint8_t* __restrict__ out) {
-    for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
-        const uint64_t it = items[k];
-        const uint64_t ci = it >> 32, at = (uint64_t)(uint32_t)it * kPiece;
-        const uint64_t len = ooff[ci + 1] - ooff[ci];
-        const uint64_t m = len - at < kPiece ? len - at : kPiece;
-        const uint8_t* const s = blobs + spans[2 * ci] + at;
-        uint8_t* const d = out + ooff[ci] + at;
-        const uint64_t full = m & ~(uint64_t)15;
-        for (uint64_t o = 16ull * threadIdx.x; o < full; o += 16ull * kThreads)
-            *reinterpret_cast<u32x4_u*>(d + o) = *reinterpret_cast<const u32x4_u*>(s + o);
-        if (threadIdx.x < m - full) d[full + threadIdx.x] = s[full + threadIdx.x];
-    }
 }
 
 __global__ void gcm_open_prepare_kernel(const KeyDev* __restrict__ key, const uint8_t* __restrict__ blobs,
@@ -304,7 +281,9 @@ __global__ void verdict_kernel(const uint8_t* __restrict__ kind, const uint8_t* 
                         dig_ok, expect_sizes != nullptr, size_ok);
 }
 
-// one workgroup per blob: zeros over the output range of an encrypted blob that failed
+// one workgroup per blob: zeros over the output range of an encrypted blob that failed.  Not
+// items of segment_copy_kernel with src == 0: which blobs failed is in d_status alone at this
+// point of the stream, and a host-built item list would cost a synchronisation to read it.
 __global__ __launch_bounds__(kThreads) void wipe_kernel(const uint8_t* __restrict__ kind,
                                                         const uint8_t* __restrict__ status,
                                                         const uint64_t* __restrict__ ooff, uint64_t n,
@@ -346,6 +325,29 @@ void host_tag(const KeyDev& k, const uint32_t j0w[4], const uint8_t* ct, size_t 
 void decode_release() {
     dec::dpool().clear();
     inflate::inflate_release();
+}
+
+size_t digest_order(const uint8_t* cls, const uint64_t* bounds, uint32_t stride, size_t n, std::vector<uint32_t>& ord) {
+    ord.clear();
+    size_t nplain = 0;
+    for (uint8_t c = 1; c <= 2; ++c) {
+        for (size_t i = 0; i < n; ++i)
+            if (cls[i] == c) ord.push_back((uint32_t)(stride * i));
+        if (c == 1) nplain = ord.size();
+    }
+    auto longer = [&](uint32_t a, uint32_t b) { return bounds[a + 1] - bounds[a] > bounds[b + 1] - bounds[b]; };
+    std::stable_sort(ord.begin(), ord.begin() + nplain, longer);
+    std::stable_sort(ord.begin() + nplain, ord.end(), longer);
+    return nplain;
+}
+
+int digest_in_order(const uint8_t* data_dev, uint64_t data_len, const uint64_t* bounds_dev, const uint32_t* ord_dev,
+                    size_t nplain, size_t nord, const pbs_crypt_config* cfg, uint8_t* dig_dev, hipStream_t st) {
+    int r = pbs_digest_chunks_async(data_dev, data_len, 0, bounds_dev, ord_dev, nplain, nullptr, 0, dig_dev, st);
+    if (r == PBS_OK && nord > nplain)
+        r = pbs_digest_chunks_async(data_dev, data_len, 0, bounds_dev, ord_dev + nplain, nord - nplain, cfg->id_key, 32,
+                                    dig_dev, st);
+    return r;
 }
 
 }  // namespace pbs
@@ -432,8 +434,7 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
                                       const uint64_t* expect_sizes, uint8_t* out_dev, size_t out_cap,
                                       uint64_t* out_offsets, uint8_t* kinds, uint8_t* status,
                                       pbs_blob_decode_timing* timing, void* hip_stream) {
-    using Clock = std::chrono::steady_clock;
-    const Clock::time_point t0 = Clock::now();
+    const HClock::time_point t0 = HClock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (!out_offsets) return PBS_ERR_ARG;
     out_offsets[0] = 0;
@@ -445,24 +446,17 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
     if (out_cap < bound) return PBS_ERR_CAPACITY;
     if (bound && !out_dev) return PBS_ERR_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
-    int dev = 0, ncu = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return PBS_ERR_NO_DEVICE;
-    DeviceGuard dg(dev);
+    const StreamDevice sd(st);
+    if (!sd.ok) return PBS_ERR_NO_DEVICE;
+    DeviceGuard dg(sd.dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
     const KeyDev* key = nullptr;
-    if (cfg && !(key = device_key(cfg, dev))) return PBS_ERR_NOMEM;
+    if (cfg && !(key = device_key(cfg, sd.dev))) return PBS_ERR_NOMEM;
 
-    int rc = PBS_OK;
-    auto fail = [&](int r) {
-        if (rc == PBS_OK) rc = r;
-        return false;
-    };
-    auto ok = [&](hipError_t e) { return e == hipSuccess || fail(PBS_ERR_HIP); };
+    CallRc call;
     size_t tmpb = 0;
     (void)exclusive_sum_u64(nullptr, &tmpb, nullptr, nullptr, (uint32_t)(n + 1), st);
-    ArenaLease ar(dpool(), dev);
+    ArenaLease ar(dpool(), sd.dev);
     uint64_t* d_boff = ar->get<uint64_t>(kDsBoff, (n + 1) * 8);
     uint8_t* d_kind = ar->get<uint8_t>(kDsKind, n);
     uint8_t* d_pre = ar->get<uint8_t>(kDsPre, n);
@@ -482,128 +476,112 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
     if (!d_boff || !d_kind || !d_pre || !d_stored || !d_len || !d_ooff || !d_spans || !d_order || !d_crc || !d_tmp ||
         !d_tagok || !d_status || (expect_digests && (!d_dig || !d_expect || !d_digord)) ||
         (expect_sizes && !d_expsize))
-        fail(PBS_ERR_NOMEM);
+        call.fail(PBS_ERR_NOMEM);
     hipEvent_t ev[6] = {};
-    for (unsigned i = 0; i < 6 && rc == PBS_OK; ++i)
-        if (!(ev[i] = ar->event(i))) fail(PBS_ERR_HIP);
+    for (unsigned i = 0; i < 6 && call.rc == PBS_OK; ++i)
+        if (!(ev[i] = ar->event(i))) call.fail(PBS_ERR_HIP);
 
     // 1. classify, output offsets
     std::vector<uint8_t> h_pre(n);
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK) {
         (void)hipGetLastError();
-        ok(hipMemcpyAsync(d_boff, blob_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
+        call.ok(hipMemcpyAsync(d_boff, blob_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
             (!expect_digests ||
-             ok(hipMemcpyAsync(d_expect, expect_digests, 32 * n, hipMemcpyHostToDevice, st))) &&
-            (!expect_sizes || ok(hipMemcpyAsync(d_expsize, expect_sizes, n * 8, hipMemcpyHostToDevice, st))) &&
-            ok(hipEventRecord(ev[0], st));
+             call.ok(hipMemcpyAsync(d_expect, expect_digests, 32 * n, hipMemcpyHostToDevice, st))) &&
+            (!expect_sizes || call.ok(hipMemcpyAsync(d_expsize, expect_sizes, n * 8, hipMemcpyHostToDevice, st))) &&
+            call.ok(hipEventRecord(ev[0], st));
     }
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK) {
         hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, blobs_dev, d_boff,
                            (uint64_t)n, d_kind, d_pre, d_stored, d_len, d_spans, d_order);
-        ok(hipGetLastError()) && ok(exclusive_sum_u64(d_tmp, &tmpb, d_len, d_ooff, (uint32_t)(n + 1), st)) &&
-            ok(hipEventRecord(ev[1], st)) &&
-            ok(hipMemcpyAsync(out_offsets, d_ooff, (n + 1) * 8, hipMemcpyDeviceToHost, st)) &&
-            ok(hipMemcpyAsync(kinds, d_kind, n, hipMemcpyDeviceToHost, st)) &&
-            ok(hipMemcpyAsync(h_pre.data(), d_pre, n, hipMemcpyDeviceToHost, st)) && ok(hipStreamSynchronize(st));
+        call.ok(hipGetLastError()) && call.ok(exclusive_sum_u64(d_tmp, &tmpb, d_len, d_ooff, (uint32_t)(n + 1), st)) &&
+            call.ok(hipEventRecord(ev[1], st)) &&
+            call.ok(hipMemcpyAsync(out_offsets, d_ooff, (n + 1) * 8, hipMemcpyDeviceToHost, st)) &&
+            call.ok(hipMemcpyAsync(kinds, d_kind, n, hipMemcpyDeviceToHost, st)) &&
+            call.ok(hipMemcpyAsync(h_pre.data(), d_pre, n, hipMemcpyDeviceToHost, st)) && call.ok(hipStreamSynchronize(st));
     }
     // (the bound covers every outcome of the classification; checked all the same, before
     // the first write to the output)
-    if (rc == PBS_OK && out_offsets[n] > out_cap) fail(PBS_ERR_CAPACITY);
+    if (call.rc == PBS_OK && out_offsets[n] > out_cap) call.fail(PBS_ERR_CAPACITY);
 
-    // the item lists: 64 KiB pieces of the unencrypted payloads, GCM segments of the encrypted
-    std::vector<uint64_t> pitems, gitems, first(n + 1);
+    // the item lists: copy items of the unencrypted payloads (disjoint ranges of the packed
+    // output), GCM segments of the encrypted; the host vectors live until the last synchronisation
+    std::vector<CopyItem> pitems;
+    std::vector<uint64_t> gitems, first(n + 1);
     std::vector<uint32_t> digord;
     size_t ndig0 = 0;
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK) {
+        std::vector<uint8_t> cls(expect_digests ? n : 0, 0);  // digest_order: kind 0 plain, kind 2 with the id_key
         for (size_t i = 0; i < n; ++i) {
             first[i] = gitems.size();
             const uint64_t len = out_offsets[i + 1] - out_offsets[i];
             if (h_pre[i] || kinds[i] == PBS_BLOB_KIND_NONE) continue;
-            const uint64_t np = (len + kPiece - 1) / kPiece;
             if (kinds[i] < 2) {
-                for (uint64_t j = 0; j < np; ++j) pitems.push_back((uint64_t)i << 32 | j);
+                add_items(pitems, (uint64_t)(uintptr_t)blobs_dev + blob_offsets[i] + PBS_BLOB_HEADER_SIZE,
+                          (uint64_t)(uintptr_t)out_dev + out_offsets[i], len);
             } else if (cfg) {
-                for (uint64_t j = 0; j < np; ++j) gitems.push_back((uint64_t)i << 32 | j);
+                const uint64_t ns = (len + PBS_GCM_SEGMENT_BYTES - 1) / PBS_GCM_SEGMENT_BYTES;
+                for (uint64_t j = 0; j < ns; ++j) gitems.push_back((uint64_t)i << 32 | j);
             }
+            if (expect_digests)
+                cls[i] = kinds[i] == PBS_BLOB_KIND_UNCOMPRESSED ? 1 : (kinds[i] == PBS_BLOB_KIND_ENCRYPTED && cfg) ? 2 : 0;
         }
         first[n] = gitems.size();
-        if (expect_digests) {  // kind 0 first (no key), then kind 2 (id_key); longest first within each
-            auto longer = [&](uint32_t a, uint32_t b) {
-                return out_offsets[a + 1] - out_offsets[a] > out_offsets[b + 1] - out_offsets[b];
-            };
-            for (size_t i = 0; i < n; ++i)
-                if (!h_pre[i] && kinds[i] == PBS_BLOB_KIND_UNCOMPRESSED) digord.push_back((uint32_t)i);
-            ndig0 = digord.size();
-            if (cfg)
-                for (size_t i = 0; i < n; ++i)
-                    if (!h_pre[i] && kinds[i] == PBS_BLOB_KIND_ENCRYPTED) digord.push_back((uint32_t)i);
-            std::stable_sort(digord.begin(), digord.begin() + ndig0, longer);
-            std::stable_sort(digord.begin() + ndig0, digord.end(), longer);
-        }
+        if (expect_digests) ndig0 = digest_order(cls.data(), out_offsets, 1, n, digord);
     }
-    const uint64_t npi = pitems.size(), ngi = gitems.size();
-    uint64_t* d_pitems = nullptr;
+    const uint64_t ngi = gitems.size();
     uint64_t* d_gitems = nullptr;
     uint64_t* d_first = nullptr;
     B128* d_part = nullptr;
     BlobCtx* d_ctx = nullptr;
-    if (rc == PBS_OK) {
-        d_pitems = ar->get<uint64_t>(kDsPItems, std::max<uint64_t>(npi, 1) * 8);
+    if (call.rc == PBS_OK) {
         d_gitems = ar->get<uint64_t>(kDsItems, std::max<uint64_t>(ngi, 1) * 8);
         d_first = ar->get<uint64_t>(kDsFirst, (n + 1) * 8);
         d_part = ar->get<B128>(kDsPart, std::max<uint64_t>(ngi, 1) * sizeof(B128));
         d_ctx = ar->get<BlobCtx>(kDsCtx, n * sizeof(BlobCtx));
-        if (!d_pitems || !d_gitems || !d_first || !d_part || !d_ctx) fail(PBS_ERR_NOMEM);
+        if (!d_gitems || !d_first || !d_part || !d_ctx) call.fail(PBS_ERR_NOMEM);
     }
-    if (rc == PBS_OK)
-        (!npi || ok(hipMemcpyAsync(d_pitems, pitems.data(), npi * 8, hipMemcpyHostToDevice, st))) &&
-            (!ngi || ok(hipMemcpyAsync(d_gitems, gitems.data(), ngi * 8, hipMemcpyHostToDevice, st))) &&
-            ok(hipMemcpyAsync(d_first, first.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
+    if (call.rc == PBS_OK)
+        (!ngi || call.ok(hipMemcpyAsync(d_gitems, gitems.data(), ngi * 8, hipMemcpyHostToDevice, st))) &&
+            call.ok(hipMemcpyAsync(d_first, first.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
             (digord.empty() ||
-             ok(hipMemcpyAsync(d_digord, digord.data(), digord.size() * 4, hipMemcpyHostToDevice, st)));
+             call.ok(hipMemcpyAsync(d_digord, digord.data(), digord.size() * 4, hipMemcpyHostToDevice, st)));
     // 2. CRCs (timed from ev[5]: the host built the lists while the stream was idle)
-    if (rc == PBS_OK) ok(hipEventRecord(ev[5], st));
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK) call.ok(hipEventRecord(ev[5], st));
+    if (call.rc == PBS_OK) {
         const hipError_t e = launch_crc32_spans(blobs_dev, d_spans, d_order, n, d_crc, st);
-        if (e != hipSuccess) fail(e == hipErrorOutOfMemory ? PBS_ERR_NOMEM : PBS_ERR_HIP);
-        else ok(hipEventRecord(ev[2], st));
+        if (e != hipSuccess) call.fail(e == hipErrorOutOfMemory ? PBS_ERR_NOMEM : PBS_ERR_HIP);
+        else call.ok(hipEventRecord(ev[2], st));
     }
     // 3. + 4. payloads into the packed output
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK) {
         const unsigned g64 = (unsigned)((n + 63) / 64);
-        if (npi)
-            hipLaunchKernelGGL(copy_kernel, dim3((unsigned)std::min<uint64_t>(npi, (uint64_t)ncu * 8)), dim3(kThreads),
-                               0, st, blobs_dev, d_pitems, npi, d_spans, d_ooff, out_dev);
-        if (cfg) {
+        call.fail(copy_items_async(pitems, *ar, kDsPItems, sd.ncu, st));
+        if (call.rc == PBS_OK && cfg) {
             hipLaunchKernelGGL(gcm_open_prepare_kernel, dim3(g64), dim3(64), 0, st, key, blobs_dev, d_boff, d_kind,
                                d_pre, (uint64_t)n, d_ctx);
             if (ngi)
                 hipLaunchKernelGGL(gcm_open_kernel,
-                                   dim3((unsigned)std::min<uint64_t>(ngi, (uint64_t)ncu * kGroupsPerCu)),
+                                   dim3((unsigned)std::min<uint64_t>(ngi, (uint64_t)sd.ncu * kGroupsPerCu)),
                                    dim3(kThreads), 0, st, key, d_gitems, ngi, d_boff, d_ooff, d_ctx, blobs_dev, out_dev,
                                    d_part);
             hipLaunchKernelGGL(gcm_open_tag_kernel, dim3(g64), dim3(64), 0, st, key, blobs_dev, d_boff, d_ooff, d_kind,
                                d_pre, d_first, d_ctx, d_part, (uint64_t)n, d_tagok);
         }
-        ok(hipGetLastError()) && ok(hipEventRecord(ev[3], st));
+        call.ok(hipGetLastError()) && call.ok(hipEventRecord(ev[3], st));
     }
     // 5. + 6. digests, verdicts, wipe
-    if (rc == PBS_OK && expect_digests) {
-        int r = pbs_digest_chunks_async(out_dev, out_offsets[n], 0, d_ooff, d_digord, ndig0, nullptr, 0, d_dig, st);
-        if (r == PBS_OK && digord.size() > ndig0)
-            r = pbs_digest_chunks_async(out_dev, out_offsets[n], 0, d_ooff, d_digord + ndig0, digord.size() - ndig0,
-                                        cfg->id_key, 32, d_dig, st);
-        if (r != PBS_OK) fail(r);
-    }
-    if (rc == PBS_OK) {
+    if (call.rc == PBS_OK && expect_digests)
+        call.fail(digest_in_order(out_dev, out_offsets[n], d_ooff, d_digord, ndig0, digord.size(), cfg, d_dig, st));
+    if (call.rc == PBS_OK) {
         hipLaunchKernelGGL(verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_kind, d_pre, d_stored,
                            d_crc, d_tagok, cfg ? 1 : 0, d_dig, d_expect, d_ooff, d_expsize, (uint64_t)n, d_status);
-        hipLaunchKernelGGL(wipe_kernel, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)ncu * 8)), dim3(kThreads), 0, st,
+        hipLaunchKernelGGL(wipe_kernel, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)sd.ncu * 8)), dim3(kThreads), 0, st,
                            d_kind, d_status, d_ooff, (uint64_t)n, out_dev);
-        ok(hipGetLastError()) && ok(hipEventRecord(ev[4], st)) &&
-            ok(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st)) && ok(hipStreamSynchronize(st));
+        call.ok(hipGetLastError()) && call.ok(hipEventRecord(ev[4], st)) &&
+            call.ok(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st)) && call.ok(hipStreamSynchronize(st));
     }
-    if (rc == PBS_OK && timing) {
+    if (call.rc == PBS_OK && timing) {
         float a = 0, b = 0, c = 0, d = 0;
         (void)hipEventElapsedTime(&a, ev[0], ev[1]);
         (void)hipEventElapsedTime(&b, ev[5], ev[2]);
@@ -618,7 +596,7 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
         timing->gcm_segments = ngi;
         for (size_t i = 0; i < n; ++i) timing->failed += status[i] != PBS_BLOB_ST_OK;
     }
-    if (rc != PBS_OK) (void)hipStreamSynchronize(st);  // the arena goes back idle
-    if (timing) timing->total_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-    return rc;
+    if (call.rc != PBS_OK) (void)hipStreamSynchronize(st);  // the arena goes back idle
+    if (timing) timing->total_ms = hms(t0);
+    return call.rc;
 }

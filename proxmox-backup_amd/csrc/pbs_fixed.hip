@@ -6,11 +6,11 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
 #include "dev_arena.h"
+#include "dev_copy.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 #include "pbs_fixed.h"
@@ -23,17 +23,6 @@ constexpr uint64_t kMinChunk = 4096;     // the smallest chunk_size of the devic
 constexpr uint32_t kItemBytes = 262144;  // bytes of both images one workgroup compares per item
 constexpr int kDirtyThreads = 256;
 constexpr uint64_t kPackBytes = 1ull << 30;  // scattered long chunks packed per hybrid digest call
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// The images' addresses travel as integers; pointers made from them are marked as global
-// memory so that the loads are global_*, not flat_*, instructions (as in pbs_restore.hip).
-#define PBS_GLOBAL __attribute__((address_space(1)))
-typedef const PBS_GLOBAL uint8_t* gcbytes;
-// 16 bytes from any address: one global load of four dwords at alignment 1
-struct __attribute__((packed, aligned(1))) U16Unaligned {
-    u32x4 v;
-};
-__device__ __forceinline__ u32x4 load16(gcbytes p) { return reinterpret_cast<const PBS_GLOBAL U16Unaligned*>(p)->v; }
 
 // Item k is bytes [k * item, min((k + 1) * item, size)) of both images, item = min(chunk_size,
 // kItemBytes): both are powers of two, so an item never straddles a chunk and its chunk is
@@ -94,11 +83,6 @@ int check_chunk_size(uint64_t chunk_size) {
     return chunk_size < kMinChunk ? PBS_ERR_INVALID : PBS_OK;
 }
 
-using HClock = std::chrono::steady_clock;
-double hms(HClock::time_point a, HClock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-}
-
 }  // namespace
 }  // namespace fixed
 }  // namespace pbs
@@ -114,17 +98,15 @@ extern "C" int pbs_fixed_dirty_device(const uint8_t* prev_dev, const uint8_t* cu
     if (size == 0) return PBS_OK;
     if (!prev_dev || !cur_dev || !dirty_dev) return PBS_ERR_INVALID;
     hipStream_t st = (hipStream_t)hip_stream;
-    int dev = 0, ncu = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return PBS_ERR_NO_DEVICE;
-    DeviceGuard dg(dev);
+    const StreamDevice sd(st);
+    if (!sd.ok) return PBS_ERR_NO_DEVICE;
+    DeviceGuard dg(sd.dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
     const uint64_t n = pbs_fidx_count(size, chunk_size);
     const uint32_t item = (uint32_t)std::min<uint64_t>(chunk_size, kItemBytes);
     const uint32_t item_shift = (uint32_t)__builtin_ctzll(chunk_size / item);
     const uint64_t nitems = size / item + (size % item ? 1 : 0);
-    ArenaLease ar(fpool(), dev);
+    ArenaLease ar(fpool(), sd.dev);
     unsigned long long* d_count = n_dirty ? ar->get<unsigned long long>(0, 8) : nullptr;
     if (n_dirty && !d_count) return PBS_ERR_NOMEM;
     int rc = PBS_OK;
@@ -132,14 +114,14 @@ extern "C" int pbs_fixed_dirty_device(const uint8_t* prev_dev, const uint8_t* cu
     if (hipMemsetAsync(dirty_dev, 0, n, st) != hipSuccess) {
         rc = PBS_ERR_HIP;
     } else {
-        const unsigned grid = (unsigned)std::min<uint64_t>(nitems, (uint64_t)std::max(ncu, 1) * 8);
+        const unsigned grid = (unsigned)std::min<uint64_t>(nitems, (uint64_t)std::max(sd.ncu, 1) * 8);
         hipLaunchKernelGGL(fixed_dirty_kernel, dim3(grid), dim3(kDirtyThreads), 0, st, (uint64_t)(uintptr_t)prev_dev,
                            (uint64_t)(uintptr_t)cur_dev, size, item, item_shift, nitems, dirty_dev);
         if (hipGetLastError() != hipSuccess) rc = PBS_ERR_HIP;
     }
     unsigned long long cnt = 0;
     if (rc == PBS_OK && n_dirty) {
-        const unsigned cgrid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(ncu, 1) * 4);
+        const unsigned cgrid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(sd.ncu, 1) * 4);
         if (hipMemsetAsync(d_count, 0, 8, st) != hipSuccess) {
             rc = PBS_ERR_HIP;
         } else {
@@ -194,11 +176,11 @@ extern "C" int pbs_fixed_digests_device(const uint8_t* dev_data, uint64_t size, 
         // are packed into scratch by the segment copy kernel, up to kPackBytes per call (one
         // hybrid call per run of indices cost a synchronisation and a one-chunk host share
         // each: 1.7 ms per run, profiles/fixed/)
-        int dev = 0;
-        if (hipStreamGetDevice(st, &dev) != hipSuccess) return PBS_ERR_NO_DEVICE;
-        DeviceGuard dg(dev);
+        const StreamDevice sd(st);
+        if (!sd.ok) return PBS_ERR_NO_DEVICE;
+        DeviceGuard dg(sd.dev);
         if (!dg.ok) return PBS_ERR_NO_DEVICE;
-        ArenaLease ar(fpool(), dev);
+        ArenaLease ar(fpool(), sd.dev);
         const uint64_t pack_cap = std::max<uint64_t>(kPackBytes, chunk_size);
         uint8_t* d_pack = ar->get<uint8_t>(4, std::min<uint64_t>(pack_cap, hashed_bytes), false);
         if (!d_pack) return PBS_ERR_NOMEM;
@@ -229,13 +211,13 @@ extern "C" int pbs_fixed_digests_device(const uint8_t* dev_data, uint64_t size, 
         }
         if (hipStreamSynchronize(st) != hipSuccess && rc == PBS_OK) rc = PBS_ERR_HIP;  // (before the arena goes back)
     } else if (g) {
-        int dev = 0;
-        if (hipStreamGetDevice(st, &dev) != hipSuccess) return PBS_ERR_NO_DEVICE;
-        DeviceGuard dg(dev);
+        const StreamDevice sd(st);
+        if (!sd.ok) return PBS_ERR_NO_DEVICE;
+        DeviceGuard dg(sd.dev);
         if (!dg.ok) return PBS_ERR_NO_DEVICE;
         // the short last chunk, if it is to be hashed, at the end of the order: the lanes of a
         // wave then hold equal lengths (the order is "longest first" already)
-        ArenaLease ar(fpool(), dev);
+        ArenaLease ar(fpool(), sd.dev);
         uint64_t* d_bounds = ar->get<uint64_t>(1, (n + 1) * 8);
         uint32_t* d_order = ar->get<uint32_t>(2, g * 4);
         uint8_t* d_dig = ar->get<uint8_t>(3, n * 32);
@@ -264,7 +246,7 @@ extern "C" int pbs_fixed_digests_device(const uint8_t* dev_data, uint64_t size, 
     }
     if (rc == PBS_OK && index_csum) pbs_sha256(digests, 32 * n, index_csum);
     if (timing) {
-        timing->total_ms = hms(t0, HClock::now());
+        timing->total_ms = hms(t0);
         timing->gpu_ms = gpu_ms;
         timing->hashed_chunks = g;
         timing->hashed_bytes = hashed_bytes;

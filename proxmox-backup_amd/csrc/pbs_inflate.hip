@@ -53,12 +53,12 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <numeric>
 #include <vector>
 
 #include "dev_arena.h"
+#include "dev_copy.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
@@ -309,39 +309,6 @@ __global__ __launch_bounds__(kThreads) void inflate_kernel(const uint8_t* __rest
 
 
 // ---- pbs_blob_decode_inflate_device: payloads into the caller's slots ---------------------
-constexpr uint32_t kPiece = 65536;  // bytes one workgroup copies
-
-// item = blob << 32 | piece: bytes [piece * 64 KiB, ...) of packed payload `blob`, cut at the
-// slot's size, into the slot (any alignment on both sides)
-__global__ __launch_bounds__(256) void slot_copy_kernel(const uint8_t* __restrict__ packed,
-                                                        const uint64_t* __restrict__ poff,
-                                                        const uint64_t* __restrict__ ooff,
-                                                        const uint64_t* __restrict__ items, uint64_t nitems,
-                                                        uint8_t* __restrict__ out) {
-    for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
-        const uint64_t it = items[k];
-        const uint64_t i = it >> 32, at = (uint64_t)(uint32_t)it * kPiece;
-        const uint64_t plen = poff[i + 1] - poff[i], slot = ooff[i + 1] - ooff[i];
-        const uint64_t len = plen < slot ? plen : slot;
-        if (at >= len) continue;
-        const uint64_t m = len - at < kPiece ? len - at : kPiece;
-        const uint8_t* const s = packed + poff[i] + at;
-        uint8_t* const d = out + ooff[i] + at;
-        for (uint64_t o = threadIdx.x; o < m; o += 256) d[o] = s[o];
-    }
-}
-
-// zeros over the whole slot of every listed blob
-__global__ __launch_bounds__(256) void slot_wipe_kernel(const uint64_t* __restrict__ ooff,
-                                                        const uint32_t* __restrict__ list, uint64_t nlist,
-                                                        uint8_t* __restrict__ out) {
-    for (uint64_t k = blockIdx.x; k < nlist; k += gridDim.x) {
-        const uint32_t i = list[k];
-        const uint64_t e = ooff[i + 1];
-        for (uint64_t o = ooff[i] + threadIdx.x; o < e; o += 256) out[o] = 0;
-    }
-}
-
 ArenaPool& ipool() {
     static ArenaPool* p = new ArenaPool;  // never destroyed (HIP may be torn down first at exit)
     return *p;
@@ -385,8 +352,7 @@ using namespace pbs::inflate;
 extern "C" int pbs_zstd_inflate_device(const uint8_t* frames_dev, const uint64_t* frame_offsets, size_t n,
                                        uint8_t* out_dev, const uint64_t* out_offsets, uint64_t* out_lens,
                                        uint8_t* status, pbs_zstd_inflate_timing* timing, void* hip_stream) {
-    using Clock = std::chrono::steady_clock;
-    const Clock::time_point t0 = Clock::now();
+    const HClock::time_point t0 = HClock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (n == 0) return PBS_OK;
     if (!frames_dev || !frame_offsets || !out_offsets || !out_lens || !status || n >= 0x7FFFFFFFull) return PBS_ERR_ARG;
@@ -394,11 +360,9 @@ extern "C" int pbs_zstd_inflate_device(const uint8_t* frames_dev, const uint64_t
         if (frame_offsets[i] > frame_offsets[i + 1] || out_offsets[i] > out_offsets[i + 1]) return PBS_ERR_ARG;
     if (out_offsets[n] > out_offsets[0] && !out_dev) return PBS_ERR_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
-    int dev = 0, ncu = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return PBS_ERR_NO_DEVICE;
-    DeviceGuard dg(dev);
+    const StreamDevice sd(st);
+    if (!sd.ok) return PBS_ERR_NO_DEVICE;
+    DeviceGuard dg(sd.dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
 
     // longest frame first: the tail of the batch is made of short ones
@@ -408,7 +372,7 @@ extern "C" int pbs_zstd_inflate_device(const uint8_t* frames_dev, const uint64_t
         return frame_offsets[a + 1] - frame_offsets[a] > frame_offsets[b + 1] - frame_offsets[b];
     });
 
-    ArenaLease ar(ipool(), dev);
+    ArenaLease ar(ipool(), sd.dev);
     uint64_t* d_foff = ar->get<uint64_t>(kIsFoff, (n + 1) * 8);
     uint64_t* d_ooff = ar->get<uint64_t>(kIsOoff, (n + 1) * 8);
     uint32_t* d_order = ar->get<uint32_t>(kIsOrder, n * 4);
@@ -426,7 +390,7 @@ extern "C" int pbs_zstd_inflate_device(const uint8_t* frames_dev, const uint64_t
         hipEventRecord(e0, st) != hipSuccess)
         rc = PBS_ERR_HIP;
     if (rc == PBS_OK)
-        rc = inflate_async(frames_dev, d_foff, d_ooff, d_order, n, out_dev, d_lens, d_status, *ar, kIsCounter, ncu, st, &grid);
+        rc = inflate_async(frames_dev, d_foff, d_ooff, d_order, n, out_dev, d_lens, d_status, *ar, kIsCounter, sd.ncu, st, &grid);
     if (rc == PBS_OK &&
         (hipEventRecord(e1, st) != hipSuccess ||
          hipMemcpyAsync(out_lens, d_lens, n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -446,24 +410,25 @@ extern "C" int pbs_zstd_inflate_device(const uint8_t* frames_dev, const uint64_t
             timing->failed += status[i] != PBS_ZST_OK;
         }
     }
-    if (timing) timing->total_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+    if (timing) timing->total_ms = hms(t0);
     return rc;
 }
 
 // DataBlob::load_from_reader + decode + verify for a stream of blobs, the inflate included:
 // pbs_blob_decode_device (classify, CRC, GCM open; its contract and code unchanged) packs the
 // payloads into arena scratch; kinds 0 and 2 are copied and kinds 1 and 3 inflated into the
-// caller's slots; the digests of all four kinds are taken over [slot, slot + out_len); the
-// verdict follows the reference's order (decrypt, decode_all, verify_digest, the length);
-// the slot of every encrypted blob that failed is zeroed.
+// caller's slots (the copies as items of segment_copy_kernel, dev_copy.h: the slots are
+// disjoint, so are the items of a launch); the digests of all four kinds are taken over
+// [slot, slot + out_len); the verdict follows the reference's order (decrypt, decode_all,
+// verify_digest, the length); the slot of every encrypted blob that failed is zeroed by zero
+// items of the same kernel, in a later launch.
 extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const uint64_t* blob_offsets, size_t n,
                                               const pbs_crypt_config* cfg, const uint8_t* expect_digests,
                                               const uint64_t* chunk_sizes, int sizes_exact, uint8_t* out_dev,
                                               size_t out_cap, uint64_t* out_offsets, uint64_t* out_lens,
                                               uint8_t* kinds, uint8_t* status,
                                               pbs_blob_decode_inflate_timing* timing, void* hip_stream) {
-    using Clock = std::chrono::steady_clock;
-    const Clock::time_point t0 = Clock::now();
+    const HClock::time_point t0 = HClock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (!out_offsets) return PBS_ERR_ARG;
     out_offsets[0] = 0;
@@ -477,14 +442,12 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
     }
     if (out_offsets[n] && !out_dev) return PBS_ERR_ARG;
     hipStream_t st = (hipStream_t)hip_stream;
-    int dev = 0, ncu = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return PBS_ERR_NO_DEVICE;
-    DeviceGuard dg(dev);
+    const StreamDevice sd(st);
+    if (!sd.ok) return PBS_ERR_NO_DEVICE;
+    DeviceGuard dg(sd.dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
 
-    ArenaLease ar(ipool(), dev);
+    ArenaLease ar(ipool(), sd.dev);
     // 1. classify / CRC / GCM open: the packed payloads (frames for kinds 1 and 3) in scratch
     const size_t bound = pbs_blob_decode_bound(blob_offsets, n);
     uint8_t* packed = ar->get<uint8_t>(kIsPacked, bound);
@@ -492,13 +455,21 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
     std::vector<uint64_t> poff(n + 1);
     std::vector<uint8_t> st1(n);
     pbs_blob_decode_timing t1;
-    int rc = pbs_blob_decode_device(blobs_dev, blob_offsets, n, cfg, nullptr, nullptr, packed, bound, poff.data(), kinds,
-                                    st1.data(), &t1, hip_stream);
-    if (rc != PBS_OK) return rc;
+    CallRc call;
+    if (!call.fail(pbs_blob_decode_device(blobs_dev, blob_offsets, n, cfg, nullptr, nullptr, packed, bound, poff.data(),
+                                          kinds, st1.data(), &t1, hip_stream)))
+        return call.rc;
 
     // 2. copy or inflate into the slots
-    std::vector<uint64_t> items;
-    std::vector<uint32_t> inf, wipe;
+    // (both item lists live until the last synchronisation; a slot may be copied into by the
+    // first launch and zeroed by the later one, never both in one)
+    std::vector<CopyItem> items, wipe;
+    std::vector<uint32_t> inf;
+    const uint64_t out0 = (uint64_t)(uintptr_t)out_dev;
+    auto wipe_slot = [&](size_t i) {
+        out_lens[i] = 0;
+        add_items(wipe, 0, out0 + out_offsets[i], chunk_sizes[i]);
+    };
     std::vector<uint8_t> over(n, 0);
     for (size_t i = 0; i < n; ++i) {
         const uint64_t plen = poff[i + 1] - poff[i];
@@ -507,14 +478,14 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
         const uint8_t k = kinds[i];
         if (k == PBS_BLOB_KIND_NONE) continue;
         if (st1[i] != PBS_BLOB_ST_OK) {
-            if (k >= 2) wipe.push_back((uint32_t)i);
+            if (k >= 2) wipe_slot(i);
             if (k != PBS_BLOB_KIND_UNCOMPRESSED) continue;  // (kind 0 keeps its payload bytes, as in the packed call)
         }
         if (k == PBS_BLOB_KIND_UNCOMPRESSED || k == PBS_BLOB_KIND_ENCRYPTED) {
             const uint64_t len = plen < chunk_sizes[i] ? plen : chunk_sizes[i];
             over[i] = plen > chunk_sizes[i];
             out_lens[i] = len;
-            for (uint64_t j = 0; j * kPiece < len; ++j) items.push_back((uint64_t)i << 32 | j);
+            add_items(items, (uint64_t)(uintptr_t)packed + poff[i], out0 + out_offsets[i], len);
         } else {
             inf.push_back((uint32_t)i);
         }
@@ -522,42 +493,30 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
     std::stable_sort(inf.begin(), inf.end(), [&](uint32_t a, uint32_t b) {
         return poff[a + 1] - poff[a] > poff[b + 1] - poff[b];
     });
-    const size_t nitems = items.size(), ninf = inf.size();
+    const size_t ninf = inf.size();
     uint64_t* d_poff = ar->get<uint64_t>(kIsFoff, (n + 1) * 8);
     uint64_t* d_ooff = ar->get<uint64_t>(kIsOoff, (n + 1) * 8);
     uint32_t* d_order = ar->get<uint32_t>(kIsOrder, n * 4);
     uint64_t* d_lens = ar->get<uint64_t>(kIsLens, n * 8);
     uint8_t* d_zst = ar->get<uint8_t>(kIsStatus, n);
-    uint64_t* d_items = ar->get<uint64_t>(kIsItems, std::max<size_t>(nitems, 1) * 8);
     hipEvent_t e0 = ar->event(0), e1 = ar->event(1), e2 = ar->event(2);
-    if (!d_poff || !d_ooff || !d_order || !d_lens || !d_zst || !d_items) return PBS_ERR_NOMEM;
+    if (!d_poff || !d_ooff || !d_order || !d_lens || !d_zst) return PBS_ERR_NOMEM;
     if (!e0 || !e1 || !e2) return PBS_ERR_HIP;
-    auto ok = [&](hipError_t e) {
-        if (e != hipSuccess && rc == PBS_OK) rc = PBS_ERR_HIP;
-        return rc == PBS_OK;
-    };
     (void)hipGetLastError();
     std::vector<uint64_t> zlens(n, 0);
     std::vector<uint8_t> zst(n, 0);
-    ok(hipMemcpyAsync(d_poff, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
-        ok(hipMemcpyAsync(d_ooff, out_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
-        (!ninf || ok(hipMemcpyAsync(d_order, inf.data(), ninf * 4, hipMemcpyHostToDevice, st))) &&
-        (!nitems || ok(hipMemcpyAsync(d_items, items.data(), nitems * 8, hipMemcpyHostToDevice, st))) &&
-        ok(hipEventRecord(e0, st));
-    if (rc == PBS_OK && nitems) {
-        hipLaunchKernelGGL(slot_copy_kernel, dim3((unsigned)std::min<uint64_t>(nitems, (uint64_t)ncu * 8)), dim3(256), 0,
-                           st, packed, d_poff, d_ooff, d_items, (uint64_t)nitems, out_dev);
-        ok(hipGetLastError());
-    }
-    if (rc == PBS_OK && ninf) {
-        rc = inflate_async(packed, d_poff, d_ooff, d_order, ninf, out_dev, d_lens, d_zst, *ar, kIsCounter, ncu, st, nullptr);
-        if (rc == PBS_OK)
-            ok(hipMemcpyAsync(zlens.data(), d_lens, n * 8, hipMemcpyDeviceToHost, st)) &&
-                ok(hipMemcpyAsync(zst.data(), d_zst, n, hipMemcpyDeviceToHost, st));
-    }
-    if (rc == PBS_OK) ok(hipEventRecord(e1, st));
-    if (hipStreamSynchronize(st) != hipSuccess && rc == PBS_OK) rc = PBS_ERR_HIP;
-    if (rc != PBS_OK) return rc;
+    call.ok(hipMemcpyAsync(d_poff, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
+        call.ok(hipMemcpyAsync(d_ooff, out_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
+        (!ninf || call.ok(hipMemcpyAsync(d_order, inf.data(), ninf * 4, hipMemcpyHostToDevice, st))) &&
+        call.ok(hipEventRecord(e0, st)) && call.fail(copy_items_async(items, *ar, kIsItems, sd.ncu, st));
+    if (call.rc == PBS_OK && ninf)
+        call.fail(inflate_async(packed, d_poff, d_ooff, d_order, ninf, out_dev, d_lens, d_zst, *ar, kIsCounter, sd.ncu, st,
+                                nullptr)) &&
+            call.ok(hipMemcpyAsync(zlens.data(), d_lens, n * 8, hipMemcpyDeviceToHost, st)) &&
+            call.ok(hipMemcpyAsync(zst.data(), d_zst, n, hipMemcpyDeviceToHost, st));
+    if (call.rc == PBS_OK) call.ok(hipEventRecord(e1, st));
+    call.ok(hipStreamSynchronize(st));  // (whatever came before: the arena and the item lists need an idle stream)
+    if (call.rc != PBS_OK) return call.rc;
     for (uint32_t i : inf) {
         out_lens[i] = zlens[i];
         if (zst[i] == PBS_ZST_BAD_FRAME) status[i] = PBS_BLOB_ST_BAD_FRAME;
@@ -574,37 +533,26 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
     if (expect_digests) {
         std::vector<uint64_t> b2(2 * n + 1);
         std::vector<uint32_t> ord;
+        std::vector<uint8_t> cls(n, 0);  // digest_order: kinds 0 and 1 plain, kinds 2 and 3 with the id_key
         for (size_t i = 0; i < n; ++i) {
             b2[2 * i] = out_offsets[i];
             b2[2 * i + 1] = out_offsets[i] + out_lens[i];
+            if (status[i] == PBS_BLOB_ST_OK && kinds[i] != PBS_BLOB_KIND_NONE) cls[i] = kinds[i] >= 2 ? 2 : 1;
         }
         b2[2 * n] = out_offsets[n];
-        size_t nplain = 0;
-        auto longer = [&](uint32_t a, uint32_t b) { return out_lens[a / 2] > out_lens[b / 2]; };
-        for (int keyed = 0; keyed < 2; ++keyed) {
-            for (size_t i = 0; i < n; ++i)
-                if (status[i] == PBS_BLOB_ST_OK && kinds[i] != PBS_BLOB_KIND_NONE && (kinds[i] >= 2) == (keyed == 1))
-                    ord.push_back((uint32_t)(2 * i));
-            if (!keyed) nplain = ord.size();
-        }
-        std::stable_sort(ord.begin(), ord.begin() + nplain, longer);
-        std::stable_sort(ord.begin() + nplain, ord.end(), longer);
+        const size_t nplain = digest_order(cls.data(), b2.data(), 2, n, ord);
         std::vector<uint8_t> dig(64 * n);
         if (!ord.empty()) {
             uint64_t* d_b2 = ar->get<uint64_t>(kIsBounds2, (2 * n + 1) * 8);
             uint32_t* d_ord = ar->get<uint32_t>(kIsDigOrd, n * 4);
             uint8_t* d_dig = ar->get<uint8_t>(kIsDig, 64 * n);
             if (!d_b2 || !d_ord || !d_dig) return PBS_ERR_NOMEM;
-            ok(hipMemcpyAsync(d_b2, b2.data(), (2 * n + 1) * 8, hipMemcpyHostToDevice, st)) &&
-                ok(hipMemcpyAsync(d_ord, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, st));
-            if (rc == PBS_OK && nplain)
-                rc = pbs_digest_chunks_async(out_dev, out_offsets[n], 0, d_b2, d_ord, nplain, nullptr, 0, d_dig, st);
-            if (rc == PBS_OK && ord.size() > nplain)
-                rc = pbs_digest_chunks_async(out_dev, out_offsets[n], 0, d_b2, d_ord + nplain, ord.size() - nplain,
-                                             pbs_crypt_config_id_key(cfg), 32, d_dig, st);
-            if (rc == PBS_OK) ok(hipMemcpyAsync(dig.data(), d_dig, 64 * n, hipMemcpyDeviceToHost, st));
-            if (hipStreamSynchronize(st) != hipSuccess && rc == PBS_OK) rc = PBS_ERR_HIP;
-            if (rc != PBS_OK) return rc;
+            call.ok(hipMemcpyAsync(d_b2, b2.data(), (2 * n + 1) * 8, hipMemcpyHostToDevice, st)) &&
+                call.ok(hipMemcpyAsync(d_ord, ord.data(), ord.size() * 4, hipMemcpyHostToDevice, st)) &&
+                call.fail(digest_in_order(out_dev, out_offsets[n], d_b2, d_ord, nplain, ord.size(), cfg, d_dig, st)) &&
+                call.ok(hipMemcpyAsync(dig.data(), d_dig, 64 * n, hipMemcpyDeviceToHost, st));
+            call.ok(hipStreamSynchronize(st));
+            if (call.rc != PBS_OK) return call.rc;
             for (uint32_t c : ord) {
                 const size_t i = c / 2;
                 if (std::memcmp(dig.data() + 32 * (size_t)c, expect_digests + 32 * i, 32) != 0)
@@ -617,22 +565,11 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
         if (sizes_exact && status[i] == PBS_BLOB_ST_OK && kinds[i] < 2 && out_lens[i] != chunk_sizes[i])
             status[i] = PBS_BLOB_ST_BAD_SIZE;
         if (kinds[i] != PBS_BLOB_KIND_NONE && kinds[i] >= 2 && status[i] != PBS_BLOB_ST_OK && st1[i] == PBS_BLOB_ST_OK)
-            wipe.push_back((uint32_t)i);
+            wipe_slot(i);
     }
-    for (uint32_t i : wipe) out_lens[i] = 0;
-    if (!wipe.empty()) {
-        uint32_t* d_wipe = ar->get<uint32_t>(kIsWipe, wipe.size() * 4);
-        if (!d_wipe) return PBS_ERR_NOMEM;
-        ok(hipMemcpyAsync(d_wipe, wipe.data(), wipe.size() * 4, hipMemcpyHostToDevice, st));
-        if (rc == PBS_OK) {
-            hipLaunchKernelGGL(slot_wipe_kernel, dim3((unsigned)std::min<uint64_t>(wipe.size(), (uint64_t)ncu * 8)),
-                               dim3(256), 0, st, d_ooff, d_wipe, (uint64_t)wipe.size(), out_dev);
-            ok(hipGetLastError());
-        }
-    }
-    if (rc == PBS_OK) ok(hipEventRecord(e2, st));
-    if (hipStreamSynchronize(st) != hipSuccess && rc == PBS_OK) rc = PBS_ERR_HIP;
-    if (rc == PBS_OK && timing) {
+    call.fail(copy_items_async(wipe, *ar, kIsWipe, sd.ncu, st)) && call.ok(hipEventRecord(e2, st));
+    call.ok(hipStreamSynchronize(st));  // (whatever came before: the arena and the item lists need an idle stream)
+    if (call.rc == PBS_OK && timing) {
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, e0, e1);
         (void)hipEventElapsedTime(&b, e1, e2);
@@ -647,6 +584,6 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
             timing->base.failed += status[i] != PBS_BLOB_ST_OK;
         }
     }
-    if (timing) timing->base.total_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-    return rc;
+    if (timing) timing->base.total_ms = hms(t0);
+    return call.rc;
 }

@@ -1,20 +1,95 @@
-// Device side of the restore path (include/pbs_restore.h): the digest lookup with grouping,
-// the segment copy kernel and pbs_restore_range_device, which strings them together with
-// pbs_blob_decode_inflate_device ("Restoring a stream").
+// Device side of the restore path (include/pbs_restore.h): the segment copy kernel that every
+// read-path call uses (dev_copy.h), the digest lookup with grouping and
+// pbs_restore_range_device, which strings them together with pbs_blob_decode_inflate_device
+// ("Restoring a stream").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
 #include "dev_arena.h"
+#include "dev_copy.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 #include "pbs_restore.h"
 
 namespace pbs {
+
+// ---- segment copy (dev_copy.h) -----------------------------------------------------------------
+
+// One workgroup per item, the items of a launch in any order.  The contract, for every caller:
+//  - an item's length is at most kPiece + 15 (add_items cuts segments so);
+//  - src == 0 means zeros;
+//  - the destinations of the items of one launch are pairwise disjoint (two workgroups would
+//    otherwise write the same bytes in no order);
+//  - nothing outside [dst, dst + len) is written and nothing outside [src, src + len) is read:
+//    the destination is written 16 bytes per lane on 16-byte boundaries, and the up to 15 head
+//    bytes before the first boundary and up to 15 tail bytes after the last go as bytes;
+//  - the host item vector and the arena slot outlive the stream's next synchronisation.
+__global__ __launch_bounds__(kCopyThreads) void segment_copy_kernel(const CopyItem* __restrict__ items,
+                                                                    uint64_t nitems) {
+    for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
+        const CopyItem it = items[k];
+        const gbytes d = (gbytes)it.dst;
+        const gcbytes s = (gcbytes)it.src;
+        const uint64_t len = it.len;
+        uint64_t head = (0 - it.dst) & 15;
+        if (head > len) head = len;
+        const uint64_t nvec = (len - head) >> 4;
+        const uint64_t tail = head + (nvec << 4);  // first tail byte
+        const uint32_t t = threadIdx.x;
+        PBS_GLOBAL u32x4* const dv = reinterpret_cast<PBS_GLOBAL u32x4*>(d + head);
+        if (it.src == 0) {  // (uniform)
+            if (t < head) d[t] = 0;
+            if (t < len - tail) d[tail + t] = 0;
+            const u32x4 z = {0, 0, 0, 0};
+            for (uint64_t v = t; v < nvec; v += kCopyThreads) dv[v] = z;
+            continue;
+        }
+        if (t < head) d[t] = s[t];
+        if (t < len - tail) d[tail + t] = s[tail + t];
+        const gcbytes sv = s + head;
+        uint64_t v = t;
+        // four loads in flight per lane, then their four stores
+        for (; v + 3 * kCopyThreads < nvec; v += 4 * kCopyThreads) {
+            const u32x4 a = load16(sv + 16 * v);
+            const u32x4 b = load16(sv + 16 * (v + kCopyThreads));
+            const u32x4 c = load16(sv + 16 * (v + 2 * kCopyThreads));
+            const u32x4 e = load16(sv + 16 * (v + 3 * kCopyThreads));
+            dv[v] = a;
+            dv[v + kCopyThreads] = b;
+            dv[v + 2 * kCopyThreads] = c;
+            dv[v + 3 * kCopyThreads] = e;
+        }
+        for (; v < nvec; v += kCopyThreads) dv[v] = load16(sv + 16 * v);
+    }
+}
+
+void add_items(std::vector<CopyItem>& items, uint64_t src, uint64_t dst, uint64_t len) {
+    if (len == 0) return;
+    uint64_t at = 0, m = std::min<uint64_t>(len, ((0 - dst) & 15) + kPiece);
+    for (;;) {
+        items.push_back({src ? src + at : 0, dst + at, m});
+        at += m;
+        if (at >= len) break;
+        m = std::min<uint64_t>(len - at, kPiece);
+    }
+}
+
+int copy_items_async(const std::vector<CopyItem>& items, DevArena& ar, unsigned slot, int ncu, hipStream_t st) {
+    if (items.empty()) return PBS_OK;
+    CopyItem* d_items = ar.get<CopyItem>(slot, items.size() * sizeof(CopyItem));
+    if (!d_items) return PBS_ERR_NOMEM;
+    if (hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(CopyItem), hipMemcpyHostToDevice, st) != hipSuccess)
+        return PBS_ERR_HIP;
+    (void)hipGetLastError();
+    const unsigned grid = (unsigned)std::min<uint64_t>(items.size(), (uint64_t)std::max(ncu, 1) * 8);
+    hipLaunchKernelGGL(segment_copy_kernel, dim3(grid), dim3(kCopyThreads), 0, st, d_items, (uint64_t)items.size());
+    return hipGetLastError() == hipSuccess ? PBS_OK : PBS_ERR_HIP;
+}
+
 namespace restore {
 namespace {
 
@@ -95,84 +170,6 @@ __global__ void lookup_kernel(const uint8_t* __restrict__ dig, uint64_t n, const
     if (rep == i) atomicAdd(&counts[1], 1u);
 }
 
-// ---- segment copy ----------------------------------------------------------------------------
-
-constexpr uint32_t kPiece = 65536;  // bytes one workgroup moves per item
-constexpr int kCopyThreads = 256;
-
-// One work item: `len` <= kPiece (+ 15 head bytes) bytes from `src` to `dst`; src == 0: zeros.
-struct CopyItem {
-    uint64_t src, dst, len;
-};
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// The items carry addresses as integers; pointers made from them are marked as global memory
-// so that the loads and stores are global_*, not flat_*, instructions.
-#define PBS_GLOBAL __attribute__((address_space(1)))
-typedef PBS_GLOBAL uint8_t* gbytes;
-typedef const PBS_GLOBAL uint8_t* gcbytes;
-// 16 bytes from any address: one global load of four dwords at alignment 1 (gfx950 reads
-// global memory at any alignment; DESIGN.md section 10 on why not two aligned loads)
-struct __attribute__((packed, aligned(1))) U16Unaligned {
-    u32x4 v;
-};
-__device__ __forceinline__ u32x4 load16(gcbytes p) { return reinterpret_cast<const PBS_GLOBAL U16Unaligned*>(p)->v; }
-
-// The destination is written 16 bytes per lane on 16-byte boundaries; up to 15 head bytes
-// before the first boundary and up to 15 tail bytes after the last are written as bytes, so
-// no byte outside [dst, dst + len) is touched and no byte outside [src, src + len) is read.
-__global__ __launch_bounds__(kCopyThreads) void segment_copy_kernel(const CopyItem* __restrict__ items,
-                                                                    uint64_t nitems) {
-    for (uint64_t k = blockIdx.x; k < nitems; k += gridDim.x) {
-        const CopyItem it = items[k];
-        const gbytes d = (gbytes)it.dst;
-        const gcbytes s = (gcbytes)it.src;
-        const uint64_t len = it.len;
-        uint64_t head = (0 - it.dst) & 15;
-        if (head > len) head = len;
-        const uint64_t nvec = (len - head) >> 4;
-        const uint64_t tail = head + (nvec << 4);  // first tail byte
-        const uint32_t t = threadIdx.x;
-        PBS_GLOBAL u32x4* const dv = reinterpret_cast<PBS_GLOBAL u32x4*>(d + head);
-        if (it.src == 0) {  // (uniform)
-            if (t < head) d[t] = 0;
-            if (t < len - tail) d[tail + t] = 0;
-            const u32x4 z = {0, 0, 0, 0};
-            for (uint64_t v = t; v < nvec; v += kCopyThreads) dv[v] = z;
-            continue;
-        }
-        if (t < head) d[t] = s[t];
-        if (t < len - tail) d[tail + t] = s[tail + t];
-        const gcbytes sv = s + head;
-        uint64_t v = t;
-        // four loads in flight per lane, then their four stores
-        for (; v + 3 * kCopyThreads < nvec; v += 4 * kCopyThreads) {
-            const u32x4 a = load16(sv + 16 * v);
-            const u32x4 b = load16(sv + 16 * (v + kCopyThreads));
-            const u32x4 c = load16(sv + 16 * (v + 2 * kCopyThreads));
-            const u32x4 e = load16(sv + 16 * (v + 3 * kCopyThreads));
-            dv[v] = a;
-            dv[v + kCopyThreads] = b;
-            dv[v + 2 * kCopyThreads] = c;
-            dv[v + 3 * kCopyThreads] = e;
-        }
-        for (; v < nvec; v += kCopyThreads) dv[v] = load16(sv + 16 * v);
-    }
-}
-
-// the items of one segment: the first ends on the destination's first 16-byte boundary + 64 KiB,
-// so every later piece starts on a boundary and has no head bytes
-void add_items(std::vector<CopyItem>& items, uint64_t src, uint64_t dst, uint64_t len) {
-    if (len == 0) return;
-    uint64_t at = 0, m = std::min<uint64_t>(len, ((0 - dst) & 15) + kPiece);
-    for (;;) {
-        items.push_back({src ? src + at : 0, dst + at, m});
-        at += m;
-        if (at >= len) break;
-        m = std::min<uint64_t>(len - at, kPiece);
-    }
-}
-
 ArenaPool& rpool() {
     static ArenaPool* p = new ArenaPool;  // never destroyed (HIP may be torn down first at exit)
     return *p;
@@ -184,20 +181,6 @@ ArenaPool& lpool() {
 ArenaPool& cpool() {
     static ArenaPool* p = new ArenaPool;
     return *p;
-}
-
-// launches the items on `st` from slot `slot` of `ar`; the caller synchronises before `items`
-// or the arena go away
-int copy_items_async(const std::vector<CopyItem>& items, DevArena& ar, unsigned slot, int ncu, hipStream_t st) {
-    if (items.empty()) return PBS_OK;
-    CopyItem* d_items = ar.get<CopyItem>(slot, items.size() * sizeof(CopyItem));
-    if (!d_items) return PBS_ERR_NOMEM;
-    if (hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(CopyItem), hipMemcpyHostToDevice, st) != hipSuccess)
-        return PBS_ERR_HIP;
-    (void)hipGetLastError();
-    const unsigned grid = (unsigned)std::min<uint64_t>(items.size(), (uint64_t)std::max(ncu, 1) * 8);
-    hipLaunchKernelGGL(segment_copy_kernel, dim3(grid), dim3(kCopyThreads), 0, st, d_items, (uint64_t)items.size());
-    return hipGetLastError() == hipSuccess ? PBS_OK : PBS_ERR_HIP;
 }
 
 struct Range {
@@ -227,20 +210,6 @@ bool segments_disjoint(uint64_t src, uint64_t dst, const uint64_t* so, const uin
         if (it != d.end() && it->lo < hi) return false;
     }
     return true;
-}
-
-struct StreamDevice {
-    int dev = 0, ncu = 0;
-    bool ok = false;
-    explicit StreamDevice(hipStream_t st) {
-        ok = hipStreamGetDevice(st, &dev) == hipSuccess &&
-             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
-    }
-};
-
-using HClock = std::chrono::steady_clock;
-double hms(HClock::time_point a, HClock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
 enum RSlot : unsigned { kRsDigests, kRsStore, kRsPos, kRsFirst, kRsPacked, kRsChunks, kRsItems, kRsRetry };
@@ -547,7 +516,7 @@ done:
         timing->blob_bytes = blob_bytes;
         timing->decoded_bytes = chunk_bytes;
         timing->out_bytes = len;
-        timing->total_ms = hms(t0, HClock::now());
+        timing->total_ms = hms(t0);
     }
     return rc;
 }

@@ -40,6 +40,7 @@
 #include "pbs_digest.h"
 #include "pbs_restore.h"
 #include "pbs_fixed.h"
+#include "pbs_gc.h"
 
 namespace pbs {
 
@@ -765,6 +766,100 @@ class FixedIndexWriter {
     int64_t ctime_;
     std::vector<uint8_t> digests_, image_;
     bool closed_ = false;
+};
+
+// One garbage collection run (include/pbs_gc.h) over a chunk store's listing: digests (32 bytes
+// per entry) and flags (PBS_GC_BAD / PBS_GC_FOREIGN).  device == true: the table lives in the
+// memory of hip_stream's device and mark() takes device addresses; false: the host mirror.
+class GarbageCollector {
+  public:
+    struct Sweep {
+        std::vector<uint8_t> actions;  // PBS_GC_KEEP / PBS_GC_PENDING / PBS_GC_REMOVE per entry
+        pbs_gc_status status;
+    };
+
+    GarbageCollector(const std::vector<uint8_t>& digests, const std::vector<uint8_t>& flags, bool device = true,
+                     void* hip_stream = nullptr)
+        : m_(flags.size()), device_(device) {
+        if (digests.size() != 32 * m_) throw std::invalid_argument("32 bytes of digest per flag");
+        const int rc = device_ ? pbs_gc_begin(digests.data(), flags.data(), m_, &dev_, &build_ms, hip_stream)
+                               : pbs_gc_begin_host(digests.data(), flags.data(), m_, &host_, &build_ms);
+        check(rc, "pbs_gc_begin");
+    }
+    ~GarbageCollector() { close(); }
+    GarbageCollector(const GarbageCollector&) = delete;
+    GarbageCollector& operator=(const GarbageCollector&) = delete;
+
+    double build_ms = 0, mark_ms = 0, sweep_ms = 0;  // of the last such call
+
+    void close() {
+        if (dev_) pbs_gc_end(dev_);
+        if (host_) pbs_gc_end_host(host_);
+        dev_ = nullptr;
+        host_ = nullptr;
+    }
+    size_t entries() const { return m_; }
+
+    // The positions of the missing entries (ascending, at most `cap`) among the n digests at
+    // base + i * stride; *n_missing counts them all.  index_bytes: one index file (counted in the
+    // status); std::nullopt: a piece of one.
+    std::vector<uint32_t> mark(const uint8_t* base, size_t stride, size_t n, std::optional<uint64_t> index_bytes,
+                               size_t cap, size_t* n_missing = nullptr) {
+        std::vector<uint32_t> pos(cap);
+        size_t nm = 0;
+        uint32_t* out = cap ? pos.data() : nullptr;
+        int rc;
+        if (device_)
+            rc = index_bytes ? pbs_gc_mark_device(dev_, base, stride, n, *index_bytes, out, cap, &nm, &mark_ms)
+                             : pbs_gc_mark_piece(dev_, base, stride, n, out, cap, &nm, &mark_ms);
+        else
+            rc = index_bytes ? pbs_gc_mark_host(host_, base, stride, n, *index_bytes, out, cap, &nm, &mark_ms)
+                             : pbs_gc_mark_piece_host(host_, base, stride, n, out, cap, &nm, &mark_ms);
+        check(rc, "pbs_gc_mark");
+        pos.resize(std::min(cap, nm));
+        if (n_missing) *n_missing = nm;
+        return pos;
+    }
+    // A whole .didx / .fidx image (host memory): the positions of all its missing entries.
+    std::vector<uint32_t> mark_index(const uint8_t* image, size_t len, size_t* n_missing = nullptr) {
+        const size_t cap = len > 4096 ? (len - 4096) / 32 : 0;
+        std::vector<uint32_t> pos(cap);
+        size_t nm = 0;
+        uint32_t* out = cap ? pos.data() : nullptr;
+        const int rc = device_ ? pbs_gc_mark_index_image(dev_, image, len, out, cap, &nm, &mark_ms)
+                               : pbs_gc_mark_index_image_host(host_, image, len, out, cap, &nm, &mark_ms);
+        check(rc, "pbs_gc_mark_index_image");
+        pos.resize(std::min(cap, nm));
+        if (n_missing) *n_missing = nm;
+        return pos;
+    }
+    std::vector<uint8_t> touched() {
+        std::vector<uint8_t> t(m_);
+        check(device_ ? pbs_gc_touched(dev_, t.data(), nullptr) : pbs_gc_touched_host(host_, t.data(), nullptr),
+              "pbs_gc_touched");
+        return t;
+    }
+    Sweep sweep(const std::vector<uint64_t>& sizes, const std::vector<int64_t>& atimes, int64_t phase1_start,
+                int64_t oldest_writer) {
+        if (sizes.size() != m_ || atimes.size() != m_) throw std::invalid_argument("one size and atime per entry");
+        Sweep s;
+        s.actions.resize(m_);
+        check(device_ ? pbs_gc_sweep(dev_, sizes.data(), atimes.data(), phase1_start, oldest_writer, s.actions.data(),
+                                     &s.status, &sweep_ms)
+                      : pbs_gc_sweep_host(host_, sizes.data(), atimes.data(), phase1_start, oldest_writer,
+                                          s.actions.data(), &s.status, &sweep_ms),
+              "pbs_gc_sweep");
+        return s;
+    }
+
+  private:
+    static void check(int rc, const char* what) {
+        if (rc != PBS_OK) throw std::runtime_error(std::string(what) + ": " + pbs_strerror(rc));
+    }
+    size_t m_;
+    bool device_;
+    pbs_gc* dev_ = nullptr;
+    pbs_gc_host* host_ = nullptr;
 };
 
 }  // namespace pbs

@@ -83,6 +83,11 @@ EXPORTED_SYMBOLS = (
     "pbs_fidx_chunk_from_offset", "pbs_fidx_check_chunk_alignment", "pbs_fixed_dirty_device", "pbs_fixed_dirty_host",
     "pbs_fixed_digests_device", "pbs_upload_fixed_host", "pbs_upload_fixed_host_crypt",
     "pbs_restore_fixed_range_device",
+    # garbage collection (include/pbs_gc.h)
+    "pbs_gc_begin", "pbs_gc_mark_device", "pbs_gc_mark_piece", "pbs_gc_mark_index_image", "pbs_gc_touched",
+    "pbs_gc_sweep", "pbs_gc_end", "pbs_gc_release", "pbs_gc_table_log2", "pbs_gc_home_slot",
+    "pbs_gc_begin_host", "pbs_gc_mark_host", "pbs_gc_mark_piece_host", "pbs_gc_mark_index_image_host",
+    "pbs_gc_touched_host", "pbs_gc_sweep_host", "pbs_gc_end_host",
 )
 
 
@@ -224,6 +229,17 @@ class UploadFixedTiming(ctypes.Structure):
         return d
 
 
+class GcStatus(ctypes.Structure):
+    """pbs_gc_status: GarbageCollectionStatus (pbs-api-types/src/datastore.rs:1308-1330) without upid."""
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "index_file_count", "index_data_bytes", "disk_bytes", "disk_chunks", "removed_bytes", "removed_chunks",
+        "pending_bytes", "pending_chunks", "removed_bad", "still_bad")]
+
+    def as_dict(self) -> dict:
+        """The kebab-case keys the reference serialises into .gc-status."""
+        return {k.replace("_", "-"): int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class HybridOpts(ctypes.Structure):
     _fields_ = [
         ("host_threads", ctypes.c_int), ("host_min_len", ctypes.c_uint64),
@@ -264,6 +280,7 @@ def lib():
             f"{LIB_PATH} not built; run `make -C proxmox-backup_amd/csrc` or __graft_entry__.build()")
     L = ctypes.CDLL(LIB_PATH)
     p, u64, sz, i = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
+    dbl = ctypes.POINTER(ctypes.c_double)
     sig = {
         "pbs_chunker_new": ([sz, ctypes.POINTER(i)], p),
         "pbs_chunker_free": ([p], None),
@@ -359,6 +376,23 @@ def lib():
                                          ctypes.POINTER(ctypes.c_double)], i),
         "pbs_restore_fixed_range_device": ([p, sz, u64, u64, p, p, p, sz, p, u64, u64, p, p,
                                             ctypes.POINTER(RestoreTiming), p], i),
+        "pbs_gc_begin": ([p, p, sz, ctypes.POINTER(p), dbl, p], i),
+        "pbs_gc_mark_device": ([p, p, sz, sz, u64, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_mark_piece": ([p, p, sz, sz, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_mark_index_image": ([p, p, sz, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_touched": ([p, p, ctypes.POINTER(sz)], i),
+        "pbs_gc_sweep": ([p, p, p, ctypes.c_int64, ctypes.c_int64, p, ctypes.POINTER(GcStatus), dbl], i),
+        "pbs_gc_end": ([p], None),
+        "pbs_gc_release": ([], None),
+        "pbs_gc_table_log2": ([p], ctypes.c_uint32),
+        "pbs_gc_home_slot": ([p, ctypes.c_uint32], u64),
+        "pbs_gc_begin_host": ([p, p, sz, ctypes.POINTER(p), dbl], i),
+        "pbs_gc_mark_host": ([p, p, sz, sz, u64, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_mark_piece_host": ([p, p, sz, sz, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_mark_index_image_host": ([p, p, sz, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_gc_touched_host": ([p, p, ctypes.POINTER(sz)], i),
+        "pbs_gc_sweep_host": ([p, p, p, ctypes.c_int64, ctypes.c_int64, p, ctypes.POINTER(GcStatus), dbl], i),
+        "pbs_gc_end_host": ([p], None),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
@@ -1977,3 +2011,250 @@ def restore_fixed_range_device(reader, store_blobs_dev: int, store_offsets, stor
         bad = [(int(k), int(status[k])) for k in np.flatnonzero((status != BLOB_ST_OK) & (status != BLOB_ST_NONE_REQUESTED))]
         raise ChunkerError(PBS_ERR_INVALID, f"restore: {t.failed} entries failed (entry, status): {bad[:8]}")
     return status, t.as_dict()
+
+
+# ---- garbage collection (include/pbs_gc.h) -------------------------------------------------------
+
+GC_BAD = 1       # PBS_GC_BAD: the name ends in ".bad"
+GC_FOREIGN = 2   # PBS_GC_FOREIGN: listed, but at a path phase 1 never touches
+GC_KEEP, GC_PENDING, GC_REMOVE = 0, 1, 2
+GC_VANISHED = (1 << 64) - 1  # sizes[j] of an entry that could not be stat'ed or is no regular file
+
+_HEX = frozenset(b"0123456789abcdefABCDEF")
+_HEX_LOWER = frozenset(b"0123456789abcdef")
+
+
+def gc_release() -> None:
+    """pbs_gc_release: free the idle work areas of the GC calls."""
+    lib().pbs_gc_release()
+
+
+def gc_home_slot(digest, table_log2: int) -> int:
+    """pbs_gc_home_slot: the slot at which a digest's probe of a 2^table_log2 table starts."""
+    d = _as_u8(digest)
+    if d.size != 32:
+        raise ValueError("a digest has 32 bytes")
+    return int(lib().pbs_gc_home_slot(d.ctypes.data, table_log2))
+
+
+def list_chunk_store(base):
+    """The files ``ChunkStore::get_chunk_iterator`` (pbs-datastore/src/chunk_store.rs:247-343)
+    yields under ``base/.chunks/0000 .. ffff`` (missing subdirectories are fine), with its name
+    filter (:288-296): 64 or 70 bytes, the first 64 ASCII hex digits of either case; bad = ends
+    with ".bad".  Returns (paths, digests (m, 32) uint8, flags (m) uint8).  GC_FOREIGN marks a name
+    that ``chunk_path`` never builds -- anything but 64 lower-case hex digits, or those + "." + one
+    digit + ".bad", in the subdirectory of its first four digits: phase 1 never touches such a
+    path, and it never counts as the chunk being there."""
+    root = os.path.join(os.fsencode(base), b".chunks")
+    try:
+        subs = sorted(s for s in os.listdir(root) if len(s) == 4 and all(c in _HEX_LOWER for c in s))
+    except FileNotFoundError:
+        subs = []
+    paths, digs, flags = [], [], []
+    for sub in subs:
+        try:
+            names = sorted(os.listdir(os.path.join(root, sub)))
+        except (FileNotFoundError, NotADirectoryError):
+            continue
+        for name in names:
+            if len(name) not in (64, 70) or not all(c in _HEX for c in name[:64]):
+                continue
+            f = GC_BAD if name.endswith(b".bad") else 0
+            own = all(c in _HEX_LOWER for c in name[:64]) and name[:4] == sub and (
+                len(name) == 64 or (name[64:65] == b"." and name[65:66].isdigit() and name[66:] == b".bad"))
+            if not own:
+                f |= GC_FOREIGN
+            paths.append(os.fsdecode(os.path.join(root, sub, name)))
+            digs.append(bytes.fromhex(name[:64].decode("ascii")))
+            flags.append(f)
+    digests = np.frombuffer(b"".join(digs), dtype=np.uint8).reshape(-1, 32).copy()
+    return paths, digests, np.asarray(flags, dtype=np.uint8)
+
+
+def _index_digest_span(image: bytes):
+    """(offset, stride, count bound) of the digests of a .didx / .fidx image, by its magic."""
+    if image[:8] == DIDX_MAGIC:
+        return DIDX_HEADER + 8, DIDX_ENTRY, max(0, (len(image) - DIDX_HEADER) // DIDX_ENTRY)
+    return FIDX_HEADER, 32, max(0, (len(image) - FIDX_HEADER) // 32)
+
+
+class GarbageCollector:
+    """One GC run over a chunk store's listing (``list_chunk_store``'s result, or (paths or None,
+    digests, flags)): a context manager over a pbs_gc handle (``device=True``: the table lives in
+    the memory of ``hip_stream``'s device) or over the host mirror's (``device=False``: no GPU)."""
+
+    def __init__(self, listing, device: bool = True, hip_stream: int = 0):
+        paths, digests, flags = listing
+        self.paths = list(paths) if paths is not None else None
+        self.digests = _digest_rows(digests)
+        self.flags = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8).reshape(-1))
+        self.m = int(self.digests.shape[0])
+        if self.flags.size != self.m:
+            raise ValueError(f"{self.m} digests, {self.flags.size} flags")
+        self.device = bool(device)
+        self._sfx = "" if self.device else "_host"
+        h, ms = ctypes.c_void_p(None), ctypes.c_double(0)
+        args = [self.digests.ctypes.data if self.m else None, self.flags.ctypes.data if self.m else None, self.m,
+                ctypes.byref(h), ctypes.byref(ms)]
+        if self.device:
+            rc = lib().pbs_gc_begin(*args, ctypes.c_void_p(hip_stream))
+        else:
+            rc = lib().pbs_gc_begin_host(*args)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_gc_begin" + self._sfx)
+        self._h = h
+        self.build_ms = float(ms.value)
+        self.mark_ms = 0.0   # of the last mark call
+        self.sweep_ms = 0.0  # of the last sweep
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self) -> None:
+        """pbs_gc_end.  Every later call raises ChunkerError(PBS_ERR_INVALID)."""
+        if getattr(self, "_h", None) is not None and not getattr(self, "_closed", False):
+            self._closed = True
+            (lib().pbs_gc_end if self.device else lib().pbs_gc_end_host)(self._h)
+
+    @property
+    def table_log2(self) -> int:
+        """L of the device table (2^L slots); None for the host mirror, which keeps a sorted list."""
+        return int(lib().pbs_gc_table_log2(self._h)) if self.device else None
+
+    def _fn(self, name: str):
+        return getattr(lib(), name + self._sfx)
+
+    def mark(self, base: int, stride: int, n: int, index_bytes: Optional[int] = None, cap: Optional[int] = None):
+        """pbs_gc_mark_device (``index_bytes`` given: one index file) or pbs_gc_mark_piece (None: a
+        piece, counts no file) over the n digests at address ``base`` + i * ``stride`` -- device
+        memory for a device handle, host memory for the mirror.  Returns (the first ``cap``
+        positions of missing entries, ascending; n_missing); ``cap`` defaults to n."""
+        cap = int(n) if cap is None else int(cap)
+        pos = np.zeros(cap, dtype=np.uint32)
+        nm, ms = ctypes.c_size_t(0), ctypes.c_double(0)
+        tail = [pos.ctypes.data if cap else None, cap, ctypes.byref(nm), ctypes.byref(ms)]
+        if index_bytes is None:
+            name = "pbs_gc_mark_piece"
+            rc = self._fn(name)(self._h, ctypes.c_void_p(base or None), stride, n, *tail)
+        else:
+            name = "pbs_gc_mark_device" if self.device else "pbs_gc_mark"
+            rc = self._fn(name)(self._h, ctypes.c_void_p(base or None), stride, n, int(index_bytes), *tail)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, name + self._sfx)
+        self.mark_ms = float(ms.value)
+        return pos[:min(cap, int(nm.value))], int(nm.value)
+
+    def mark_index(self, path_or_bytes, cap: Optional[int] = None) -> np.ndarray:
+        """pbs_gc_mark_index_image over a .didx / .fidx file (a path) or image (bytes): the positions
+        of its missing entries, ascending (the first ``cap``; default all).  ``n_missing`` keeps
+        the count of the last call.  A bad image raises ChunkerError and marks nothing."""
+        if isinstance(path_or_bytes, (str, os.PathLike)):
+            with open(path_or_bytes, "rb") as f:
+                image = f.read()
+        else:
+            image = bytes(path_or_bytes)
+        if cap is None:
+            cap = _index_digest_span(image)[2]
+        pos = np.zeros(cap, dtype=np.uint32)
+        nm, ms = ctypes.c_size_t(0), ctypes.c_double(0)
+        rc = self._fn("pbs_gc_mark_index_image")(self._h, image, len(image), pos.ctypes.data if cap else None, cap,
+                                                 ctypes.byref(nm), ctypes.byref(ms))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_gc_mark_index_image" + self._sfx)
+        self.mark_ms = float(ms.value)
+        self.n_missing = int(nm.value)
+        return pos[:min(cap, self.n_missing)]
+
+    def touched(self) -> np.ndarray:
+        """pbs_gc_touched: touched[j] = 1 for the entries phase 1 would have touched."""
+        t = np.zeros(self.m, dtype=np.uint8)
+        nt = ctypes.c_size_t(0)
+        rc = self._fn("pbs_gc_touched")(self._h, t.ctypes.data if self.m else None, ctypes.byref(nt))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_gc_touched" + self._sfx)
+        return t
+
+    def sweep(self, sizes, atimes, phase1_start: int, oldest_writer: int):
+        """pbs_gc_sweep: (actions (m) uint8 of GC_KEEP / GC_PENDING / GC_REMOVE, the status as a
+        dict with the reference's kebab-case keys)."""
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint64).reshape(-1))
+        at = np.ascontiguousarray(np.asarray(atimes, dtype=np.int64).reshape(-1))
+        if sz.size != self.m or at.size != self.m:
+            raise ValueError(f"the listing has {self.m} entries: {sz.size} sizes, {at.size} atimes")
+        actions = np.zeros(self.m, dtype=np.uint8)
+        st, ms = GcStatus(), ctypes.c_double(0)
+        rc = self._fn("pbs_gc_sweep")(self._h, sz.ctypes.data if self.m else None, at.ctypes.data if self.m else None,
+                                      int(phase1_start), int(oldest_writer), actions.ctypes.data if self.m else None,
+                                      ctypes.byref(st), ctypes.byref(ms))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_gc_sweep" + self._sfx)
+        self.sweep_ms = float(ms.value)
+        return actions, st.as_dict()
+
+
+def garbage_collection(base, index_paths, phase1_start: Optional[int] = None, oldest_writer: Optional[int] = None,
+                       device: bool = True, apply: bool = True):
+    """``DataStore::garbage_collection`` (pbs-datastore/src/datastore.rs:1065-1177) over the chunk
+    store under ``base`` and the given index files, in the reference's order: list the store and
+    mark every index (a vanished index file is skipped, :1029; a file that is neither .fidx nor
+    .didx is ignored, :1015); with ``apply`` set the atime of the touched files to now (mtime
+    unchanged); THEN lstat every listed file (no regular file, or gone: GC_VANISHED); sweep; with
+    ``apply`` unlink the GC_REMOVE entries.  ``phase1_start`` defaults to now (taken before the
+    marks), ``oldest_writer`` to it (no writer).  Files created after the listing are outside the
+    plan: never removed, not counted.  Returns (status dict with the keys of .gc-status, list of
+    (index path, hex digest) warnings: entries whose chunk is absent, every occurrence)."""
+    import time
+
+    if phase1_start is None:
+        phase1_start = int(time.time())
+    if oldest_writer is None:
+        oldest_writer = phase1_start
+    listing = list_chunk_store(base)
+    paths = listing[0]
+    warnings = []
+    with GarbageCollector(listing, device=device) as gc:
+        for ip in index_paths:
+            name = os.fspath(ip)
+            if not (name.endswith(".fidx") or name.endswith(".didx")):
+                continue
+            try:
+                with open(ip, "rb") as f:
+                    image = f.read()
+            except FileNotFoundError:
+                continue
+            off, stride, _ = _index_digest_span(image)
+            for pos in gc.mark_index(image):
+                at = off + stride * int(pos)
+                warnings.append((name, image[at:at + 32].hex()))
+        if apply:
+            for j in np.flatnonzero(gc.touched()):
+                try:
+                    st = os.lstat(paths[j])
+                    os.utime(paths[j], ns=(time.time_ns(), st.st_mtime_ns), follow_symlinks=False)
+                except FileNotFoundError:
+                    pass
+        import stat as _stat
+        sizes = np.full(len(paths), GC_VANISHED, dtype=np.uint64)
+        atimes = np.zeros(len(paths), dtype=np.int64)
+        for j, p in enumerate(paths):
+            try:
+                st = os.lstat(p)
+            except OSError:
+                continue
+            if _stat.S_ISREG(st.st_mode):
+                sizes[j] = st.st_size
+                atimes[j] = st.st_atime_ns // 1_000_000_000
+        actions, status = gc.sweep(sizes, atimes, phase1_start, oldest_writer)
+    if apply:
+        for j in np.flatnonzero(actions == GC_REMOVE):
+            os.unlink(paths[j])
+    return status, warnings

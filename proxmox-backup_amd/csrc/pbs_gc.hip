@@ -18,6 +18,7 @@
 
 #include "dev_arena.h"
 #include "gc_common.h"
+#include "gc_table_dev.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 #include "pbs_gc.h"
@@ -37,44 +38,6 @@ struct pbs_gc {
 namespace pbs {
 namespace gc {
 namespace {
-
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kGcThreads = 256;
-constexpr int kGcWaves = kGcThreads / 64;
-
-struct Dig {
-    uint64_t w[4];
-};
-// four 8-byte loads: the digests of a .didx image are 8- but not 16-byte aligned
-__device__ __forceinline__ Dig load_digest(const uint8_t* __restrict__ p) {
-    const uint64_t* q = reinterpret_cast<const uint64_t*>(p);
-    Dig d;
-    d.w[0] = q[0];
-    d.w[1] = q[1];
-    d.w[2] = q[2];
-    d.w[3] = q[3];
-    return d;
-}
-__device__ __forceinline__ uint64_t home_slot(uint64_t w0, uint32_t shift) {
-    return (__builtin_bswap64(w0) * kGcHashMul) >> shift;  // w0: the first 8 bytes, loaded little-endian
-}
-// does store entry j carry the digest d?  (first word first: most slots of a cluster differ there)
-__device__ __forceinline__ bool same_digest(const uint8_t* __restrict__ store, uint32_t j, const Dig& d) {
-    const uint64_t* q = reinterpret_cast<const uint64_t*>(store + 32ull * j);
-    if (q[0] != d.w[0]) return false;
-    return q[1] == d.w[1] && q[2] == d.w[2] && q[3] == d.w[3];
-}
-
-// One lane per store entry: claims the first free slot from its home slot on.  The table holds
-// 2^L >= 2 m slots, so a free slot always comes.
-__global__ __launch_bounds__(kGcThreads) void gc_build_kernel(const uint8_t* __restrict__ store, uint64_t m,
-                                                              uint32_t* __restrict__ table, uint32_t shift,
-                                                              uint64_t mask) {
-    const uint64_t j = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
-    if (j >= m) return;
-    uint64_t s = home_slot(*reinterpret_cast<const uint64_t*>(store + 32 * j), shift);
-    while (atomicCAS(&table[s], kEmpty, (uint32_t)j) != kEmpty) s = (s + 1) & mask;
-}
 
 // One lane per index entry: walks the cluster from the home slot to the first free slot, marks
 // every store entry with the entry's digest (the byte is read first: consecutive snapshots
@@ -242,8 +205,6 @@ bool alive(const pbs_gc* h) {
     std::lock_guard<std::mutex> g(l.mu);
     return l.handles.count(h) != 0;
 }
-
-inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kGcThreads - 1) / kGcThreads); }
 
 void free_handle(pbs_gc* h) {
     DeviceGuard dg(h->dev);

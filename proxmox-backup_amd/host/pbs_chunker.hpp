@@ -41,6 +41,7 @@
 #include "pbs_restore.h"
 #include "pbs_fixed.h"
 #include "pbs_gc.h"
+#include "pbs_verify.h"
 
 namespace pbs {
 
@@ -860,6 +861,131 @@ class GarbageCollector {
     bool device_;
     pbs_gc* dev_ = nullptr;
     pbs_gc_host* host_ = nullptr;
+};
+
+// The verify job's worker (include/pbs_verify.h) over a chunk store's listing (32 bytes of digest
+// per chunk file): the states of its chunks live from index to index and snapshot to snapshot.
+// device == true: table and states live in the memory of hip_stream's device and the blobs handed
+// to submit / verify_index are device memory; false: the host mirror.
+class VerifyWorker {
+  public:
+    struct Outcome {
+        pbs_verify_result result;
+        std::vector<uint32_t> corrupt_store;  // the store positions that became CORRUPT: the files to rename
+        std::vector<uint32_t> missing_pos;    // the index positions whose chunk is absent
+    };
+    struct Plan {
+        std::vector<uint32_t> todo_store, todo_entry;
+    };
+
+    explicit VerifyWorker(const std::vector<uint8_t>& digests, bool device = true, void* hip_stream = nullptr)
+        : m_(digests.size() / 32), device_(device) {
+        if (digests.size() != 32 * m_) throw std::invalid_argument("32 bytes of digest per entry");
+        const int rc = device_ ? pbs_verify_begin(digests.data(), m_, &dev_, &build_ms, hip_stream)
+                               : pbs_verify_begin_host(digests.data(), m_, &host_, &build_ms);
+        check(rc, "pbs_verify_begin");
+    }
+    ~VerifyWorker() { close(); }
+    VerifyWorker(const VerifyWorker&) = delete;
+    VerifyWorker& operator=(const VerifyWorker&) = delete;
+
+    double build_ms = 0, plan_ms = 0;  // of the last such call
+    pbs_verify_timing timing{};        // of the last submit
+
+    void close() {
+        if (dev_) pbs_verify_end(dev_);
+        if (host_) pbs_verify_end_host(host_);
+        dev_ = nullptr;
+        host_ = nullptr;
+    }
+    size_t entries() const { return m_; }
+
+    std::vector<uint8_t> states() {
+        std::vector<uint8_t> s(m_);
+        check(device_ ? pbs_verify_states(dev_, s.data(), m_) : pbs_verify_states_host(host_, s.data(), m_),
+              "pbs_verify_states");
+        return s;
+    }
+    // The chunk files to read for an index of n entries (digests: 32 n bytes, sizes: n), in read order.
+    Plan plan(const std::vector<uint8_t>& digests, const std::vector<uint64_t>& sizes, int index_mode) {
+        const size_t n = sizes.size(), cap = std::min(n, m_);
+        if (digests.size() != 32 * n) throw std::invalid_argument("32 bytes of digest per size");
+        Plan p;
+        p.todo_store.resize(cap);
+        p.todo_entry.resize(cap);
+        size_t k = 0;
+        const int rc = device_ ? pbs_verify_plan(dev_, digests.data(), sizes.data(), n, index_mode, p.todo_store.data(),
+                                                 p.todo_entry.data(), cap, &k, &plan_ms)
+                               : pbs_verify_plan_host(host_, digests.data(), sizes.data(), n, index_mode,
+                                                      p.todo_store.data(), p.todo_entry.data(), cap, &k, &plan_ms);
+        check(rc, "pbs_verify_plan");
+        p.todo_store.resize(std::min(cap, k));
+        p.todo_entry.resize(std::min(cap, k));
+        return p;
+    }
+    void abort_index() {
+        check(device_ ? pbs_verify_abort_index(dev_) : pbs_verify_abort_index_host(host_), "pbs_verify_abort_index");
+    }
+    // The plan's next blob_offsets.size() - 1 items as raw blob images; returns their status codes.
+    std::vector<uint8_t> submit(const uint8_t* blobs, const std::vector<uint64_t>& blob_offsets,
+                                const uint8_t* load_failed = nullptr, std::vector<uint8_t>* kinds = nullptr) {
+        const size_t k = blob_offsets.empty() ? 0 : blob_offsets.size() - 1;
+        std::vector<uint8_t> status(k), kd(k);
+        const int rc = device_ ? pbs_verify_submit(dev_, blobs, blob_offsets.data(), load_failed, k, kd.data(),
+                                                   status.data(), &timing)
+                               : pbs_verify_submit_host(host_, blobs, blob_offsets.data(), load_failed, k, kd.data(),
+                                                        status.data(), &timing);
+        check(rc, "pbs_verify_submit");
+        if (kinds) *kinds = kd;
+        return status;
+    }
+    // `entries`: the index's length (bounds missing_pos).
+    Outcome finish(size_t entries) {
+        Outcome o;
+        o.corrupt_store.resize(m_);
+        o.missing_pos.resize(entries);
+        size_t nc = 0, nm = 0;
+        const int rc = device_ ? pbs_verify_finish(dev_, &o.result, o.corrupt_store.data(), m_, &nc,
+                                                   o.missing_pos.data(), entries, &nm)
+                               : pbs_verify_finish_host(host_, &o.result, o.corrupt_store.data(), m_, &nc,
+                                                        o.missing_pos.data(), entries, &nm);
+        check(rc, "pbs_verify_finish");
+        o.corrupt_store.resize(std::min(m_, nc));
+        o.missing_pos.resize(std::min(entries, nm));
+        return o;
+    }
+    // A whole .didx / .fidx image against a resident store (store entry j: [store_offsets[j],
+    // store_offsets[j + 1]) of store_blobs).  info_size / info_csum: the manifest's, or nullptr.
+    Outcome verify_index(const uint8_t* image, size_t len, int index_mode, const uint64_t* info_size,
+                         const uint8_t* info_csum, const uint8_t* store_blobs,
+                         const std::vector<uint64_t>& store_offsets, size_t budget_bytes = 0) {
+        if (store_offsets.size() != m_ + 1) throw std::invalid_argument("one offset per entry and one more");
+        Outcome o;
+        const size_t entries = len > 4096 ? (len - 4096) / 32 : 0;
+        o.corrupt_store.resize(m_);
+        o.missing_pos.resize(entries);
+        size_t nc = 0, nm = 0;
+        const int rc =
+            device_ ? pbs_verify_index_device(dev_, image, len, index_mode, info_size, info_csum, store_blobs,
+                                              store_offsets.data(), budget_bytes, &o.result, o.corrupt_store.data(), m_,
+                                              &nc, o.missing_pos.data(), entries, &nm)
+                    : pbs_verify_index_host(host_, image, len, index_mode, info_size, info_csum, store_blobs,
+                                            store_offsets.data(), budget_bytes, &o.result, o.corrupt_store.data(), m_, &nc,
+                                            o.missing_pos.data(), entries, &nm);
+        check(rc, "pbs_verify_index");
+        o.corrupt_store.resize(std::min(m_, nc));
+        o.missing_pos.resize(std::min(entries, nm));
+        return o;
+    }
+
+  private:
+    static void check(int rc, const char* what) {
+        if (rc != PBS_OK) throw std::runtime_error(std::string(what) + ": " + pbs_strerror(rc));
+    }
+    size_t m_;
+    bool device_;
+    pbs_verify* dev_ = nullptr;
+    pbs_verify_host* host_ = nullptr;
 };
 
 }  // namespace pbs

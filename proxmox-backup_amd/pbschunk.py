@@ -88,6 +88,12 @@ EXPORTED_SYMBOLS = (
     "pbs_gc_sweep", "pbs_gc_end", "pbs_gc_release", "pbs_gc_table_log2", "pbs_gc_home_slot",
     "pbs_gc_begin_host", "pbs_gc_mark_host", "pbs_gc_mark_piece_host", "pbs_gc_mark_index_image_host",
     "pbs_gc_touched_host", "pbs_gc_sweep_host", "pbs_gc_end_host",
+    # the verify job (include/pbs_verify.h)
+    "pbs_verify_begin", "pbs_verify_states", "pbs_verify_end", "pbs_verify_release", "pbs_verify_plan",
+    "pbs_verify_abort_index", "pbs_verify_submit", "pbs_verify_finish", "pbs_verify_index_device",
+    "pbs_verify_blob_host", "pbs_verify_begin_host", "pbs_verify_states_host", "pbs_verify_end_host",
+    "pbs_verify_plan_host", "pbs_verify_abort_index_host", "pbs_verify_submit_host", "pbs_verify_finish_host",
+    "pbs_verify_index_host",
 )
 
 
@@ -238,6 +244,27 @@ class GcStatus(ctypes.Structure):
     def as_dict(self) -> dict:
         """The kebab-case keys the reference serialises into .gc-status."""
         return {k.replace("_", "-"): int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class VerifyResult(ctypes.Structure):
+    """pbs_verify_result: the counts of one verified index."""
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "entries", "skipped_verified", "skipped_corrupt", "loaded", "newly_verified", "newly_corrupt",
+        "mode_mismatch", "missing", "read_bytes", "decoded_bytes", "errors")] + [
+        ("ok", ctypes.c_uint32), ("index_check", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class VerifyTiming(ctypes.Structure):
+    """pbs_verify_timing: one submit."""
+    _fields_ = [("total_ms", ctypes.c_double), ("magic_ms", ctypes.c_double), ("decode_ms", ctypes.c_double),
+                ("state_ms", ctypes.c_double), ("blobs", ctypes.c_uint64), ("decoded", ctypes.c_uint64),
+                ("encrypted", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class HybridOpts(ctypes.Structure):
@@ -393,6 +420,28 @@ def lib():
         "pbs_gc_touched_host": ([p, p, ctypes.POINTER(sz)], i),
         "pbs_gc_sweep_host": ([p, p, p, ctypes.c_int64, ctypes.c_int64, p, ctypes.POINTER(GcStatus), dbl], i),
         "pbs_gc_end_host": ([p], None),
+        "pbs_verify_begin": ([p, sz, ctypes.POINTER(p), dbl, p], i),
+        "pbs_verify_states": ([p, p, sz], i),
+        "pbs_verify_end": ([p], None),
+        "pbs_verify_release": ([], None),
+        "pbs_verify_plan": ([p, p, p, sz, i, p, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_verify_abort_index": ([p], i),
+        "pbs_verify_submit": ([p, p, p, p, sz, p, p, ctypes.POINTER(VerifyTiming)], i),
+        "pbs_verify_finish": ([p, ctypes.POINTER(VerifyResult), p, sz, ctypes.POINTER(sz), p, sz,
+                               ctypes.POINTER(sz)], i),
+        "pbs_verify_index_device": ([p, p, sz, i, ctypes.POINTER(u64), p, p, p, sz, ctypes.POINTER(VerifyResult),
+                                     p, sz, ctypes.POINTER(sz), p, sz, ctypes.POINTER(sz)], i),
+        "pbs_verify_blob_host": ([p, sz, u64, p, ctypes.POINTER(i)], i),
+        "pbs_verify_begin_host": ([p, sz, ctypes.POINTER(p), dbl], i),
+        "pbs_verify_states_host": ([p, p, sz], i),
+        "pbs_verify_end_host": ([p], None),
+        "pbs_verify_plan_host": ([p, p, p, sz, i, p, p, sz, ctypes.POINTER(sz), dbl], i),
+        "pbs_verify_abort_index_host": ([p], i),
+        "pbs_verify_submit_host": ([p, p, p, p, sz, p, p, ctypes.POINTER(VerifyTiming)], i),
+        "pbs_verify_finish_host": ([p, ctypes.POINTER(VerifyResult), p, sz, ctypes.POINTER(sz), p, sz,
+                                    ctypes.POINTER(sz)], i),
+        "pbs_verify_index_host": ([p, p, sz, i, ctypes.POINTER(u64), p, p, p, sz, ctypes.POINTER(VerifyResult),
+                                   p, sz, ctypes.POINTER(sz), p, sz, ctypes.POINTER(sz)], i),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
@@ -2258,3 +2307,351 @@ def garbage_collection(base, index_paths, phase1_start: Optional[int] = None, ol
         for j in np.flatnonzero(actions == GC_REMOVE):
             os.unlink(paths[j])
     return status, warnings
+
+
+# ---- the verify job (include/pbs_verify.h) -------------------------------------------------------
+
+VERIFY_UNKNOWN, VERIFY_VERIFIED, VERIFY_CORRUPT = 0, 1, 2
+VERIFY_MODE_NONE, VERIFY_MODE_ENCRYPT = 0, 1
+VERIFY_ST_LOAD_FAILED = 32   # PBS_VERIFY_ST_LOAD_FAILED: the caller could not open or read the file
+VERIFY_INDEX_OK, VERIFY_INDEX_WRONG_SIZE, VERIFY_INDEX_WRONG_CSUM = 0, 1, 2
+(VERIFY_BLOB_OK, VERIFY_BLOB_WRONG_SIZE, VERIFY_BLOB_WRONG_CSUM, VERIFY_BLOB_LOAD, VERIFY_BLOB_DECODE) = range(5)
+_VERIFY_BLOB_ERRORS = ("", "wrong size", "wrong index checksum", "unable to load blob", "unable to decode blob")
+
+
+def verify_release() -> None:
+    """pbs_verify_release: free the idle work areas of the verify calls."""
+    lib().pbs_verify_release()
+
+
+def verify_crypt_mode(crypt_mode) -> int:
+    """``FileInfo::chunk_crypt_mode`` (pbs-datastore/src/manifest.rs:39-44) of a manifest's
+    "crypt-mode" string, or a VERIFY_MODE_* value as it is: "encrypt" is ENCRYPT, "none" and
+    "sign-only" are NONE."""
+    if isinstance(crypt_mode, str):
+        try:
+            return {"encrypt": VERIFY_MODE_ENCRYPT, "none": VERIFY_MODE_NONE, "sign-only": VERIFY_MODE_NONE}[crypt_mode]
+        except KeyError:
+            raise ValueError(f"unknown crypt mode {crypt_mode!r}") from None
+    return int(crypt_mode)
+
+
+def verify_blob(raw, info) -> int:
+    """pbs_verify_blob_host (verify.rs:48-70): ``info`` is (size, csum) of the manifest's FileInfo,
+    ``csum`` 32 bytes.  Returns VERIFY_BLOB_*: the first of raw size, SHA-256 of the raw bytes,
+    the load (size, magic, CRC), the decode of an unencrypted blob that fails."""
+    a = _as_u8(raw)
+    size, csum = info
+    csum = bytes(csum)
+    if len(csum) != 32:
+        raise ValueError("a checksum has 32 bytes")
+    res = ctypes.c_int(0)
+    rc = lib().pbs_verify_blob_host(_ptr(a), a.size, int(size), ctypes.create_string_buffer(csum, 32), ctypes.byref(res))
+    if rc != PBS_OK:
+        raise ChunkerError(rc, "pbs_verify_blob_host")
+    return int(res.value)
+
+
+def bad_chunk_path(path: str) -> str:
+    """The name ``rename_corrupted_chunk`` (verify.rs:79-88) moves a corrupt chunk to:
+    "<path>.N.bad" with the first N in 0..8 that does not exist yet -- and N = 9 whether that
+    exists or not: the reference's loop stops counting at 9 and overwrites."""
+    counter = 0
+    while True:
+        new_path = f"{path}.{counter}.bad"
+        if os.path.exists(new_path) and counter < 9:
+            counter += 1
+        else:
+            return new_path
+
+
+class VerifyWorker:
+    """``VerifyWorker`` (src/backup/verify.rs:27-46) over a chunk store's listing
+    (``list_chunk_store``'s result, or (paths or None, digests[, flags])): a context manager over a
+    pbs_verify handle (``device=True``: table and states live in the memory of ``hip_stream``'s
+    device) or over the host mirror's (``device=False``: no GPU).  Only chunk files proper belong
+    in the listing: entries whose flags are not 0 (.bad files, foreign names) are dropped.  The
+    states -- the worker's verified_chunks / corrupt_chunks -- live until ``close``."""
+
+    def __init__(self, listing, device: bool = True, hip_stream: int = 0):
+        paths, digests = listing[0], _digest_rows(listing[1])
+        if len(listing) > 2 and listing[2] is not None:
+            keep = np.flatnonzero(np.asarray(listing[2], dtype=np.uint8).reshape(-1) == 0)
+            digests = np.ascontiguousarray(digests[keep])
+            paths = [paths[j] for j in keep] if paths is not None else None
+        self.paths = list(paths) if paths is not None else None
+        self.digests = digests
+        self.m = int(digests.shape[0])
+        self.device = bool(device)
+        self._sfx = "" if self.device else "_host"
+        h, ms = ctypes.c_void_p(None), ctypes.c_double(0)
+        args = [self.digests.ctypes.data if self.m else None, self.m, ctypes.byref(h), ctypes.byref(ms)]
+        if self.device:
+            rc = lib().pbs_verify_begin(*args, ctypes.c_void_p(hip_stream))
+        else:
+            rc = lib().pbs_verify_begin_host(*args)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_begin" + self._sfx)
+        self._h = h
+        self.build_ms = float(ms.value)
+        self.plan_ms = 0.0       # of the last plan
+        self.timing = None       # of the last submit
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self) -> None:
+        """pbs_verify_end.  Every later call raises ChunkerError(PBS_ERR_INVALID)."""
+        if getattr(self, "_h", None) is not None and not getattr(self, "_closed", False):
+            self._closed = True
+            (lib().pbs_verify_end if self.device else lib().pbs_verify_end_host)(self._h)
+
+    def _fn(self, name: str):
+        return getattr(lib(), name + self._sfx)
+
+    def states(self) -> np.ndarray:
+        """pbs_verify_states: VERIFY_UNKNOWN / VERIFIED / CORRUPT per listing entry."""
+        s = np.zeros(self.m, dtype=np.uint8)
+        rc = self._fn("pbs_verify_states")(self._h, s.ctypes.data if self.m else None, self.m)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_states" + self._sfx)
+        return s
+
+    def plan(self, digests, sizes, crypt_mode):
+        """pbs_verify_plan over an index's digests (n, 32) and chunk sizes (n): (todo_store,
+        todo_entry), the store positions to read in ascending order and for each the lowest
+        index position naming it."""
+        d = _digest_rows(digests)
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint64).reshape(-1))
+        n = int(d.shape[0])
+        if sz.size != n:
+            raise ValueError(f"{n} digests, {sz.size} sizes")
+        cap = min(n, self.m)
+        ts, te = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        nt, ms = ctypes.c_size_t(0), ctypes.c_double(0)
+        rc = self._fn("pbs_verify_plan")(self._h, d.ctypes.data if n else None, sz.ctypes.data if n else None, n,
+                                         verify_crypt_mode(crypt_mode), ts.ctypes.data if cap else None,
+                                         te.ctypes.data if cap else None, cap, ctypes.byref(nt), ctypes.byref(ms))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_plan" + self._sfx)
+        self.plan_ms = float(ms.value)
+        return ts[:nt.value], te[:nt.value]
+
+    def abort_index(self) -> None:
+        """pbs_verify_abort_index: drop an unfinished plan; no state changes."""
+        rc = self._fn("pbs_verify_abort_index")(self._h)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_abort_index" + self._sfx)
+
+    def submit(self, blobs, blob_offsets, load_failed=None):
+        """pbs_verify_submit of the plan's next k items.  ``blobs``: for a device handle the device
+        address of the raw blob images, for the mirror bytes or an array; ``blob_offsets``: k + 1
+        offsets into it; ``load_failed``: None or k flags.  Returns (kinds (k), status (k))."""
+        off = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64).reshape(-1))
+        k = max(0, off.size - 1)
+        lf = None
+        if load_failed is not None:
+            lf = np.ascontiguousarray(np.asarray(load_failed, dtype=np.uint8).reshape(-1))
+            if lf.size != k:
+                raise ValueError(f"{k} blobs, {lf.size} load_failed flags")
+        if self.device:
+            ptr = ctypes.c_void_p(int(blobs) or None)
+        else:
+            keep = _as_u8(blobs)
+            ptr = _ptr(keep)
+        kinds, status = np.zeros(k, dtype=np.uint8), np.zeros(k, dtype=np.uint8)
+        t = VerifyTiming()
+        rc = self._fn("pbs_verify_submit")(self._h, ptr, off.ctypes.data if off.size else None,
+                                           None if lf is None else _ptr(lf), k, _ptr(kinds), _ptr(status),
+                                           ctypes.byref(t))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_submit" + self._sfx)
+        self.timing = t.as_dict()
+        return kinds, status
+
+    def _lists(self, n_hint: int):
+        cs = np.zeros(max(self.m, 1), dtype=np.uint32)
+        mp = np.zeros(max(int(n_hint), 1), dtype=np.uint32)
+        return cs, mp
+
+    def finish(self, n_hint: Optional[int] = None):
+        """pbs_verify_finish: (result dict, corrupt_store -- the store positions that became
+        CORRUPT in this index, ascending -- and missing_pos, the index positions whose chunk is
+        absent).  ``n_hint``: the index's length (bounds missing_pos; default 2^20 entries, and
+        the call is repeated nowhere: pass it for longer indexes)."""
+        cs, mp = self._lists((1 << 20) if n_hint is None else n_hint)
+        res, nc, nm = VerifyResult(), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = self._fn("pbs_verify_finish")(self._h, ctypes.byref(res), cs.ctypes.data, cs.size, ctypes.byref(nc),
+                                           mp.ctypes.data, mp.size, ctypes.byref(nm))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_verify_finish" + self._sfx)
+        return res.as_dict(), cs[:min(cs.size, nc.value)].copy(), mp[:min(mp.size, nm.value)].copy()
+
+    def verify_index(self, image, crypt_mode, info=None, store=None, budget: int = 0):
+        """pbs_verify_index_device / pbs_verify_index_host over a .didx / .fidx image (bytes or a
+        path).  ``info``: None or (size, csum) of the manifest's FileInfo, either of which may be
+        None; ``store``: (blobs, offsets) -- the chunk files of the listing back to back, for a
+        device handle a device address, for the mirror bytes or an array -- with m + 1 offsets;
+        ``budget``: the bound of a batch in bytes (0: none).  Returns (result dict, corrupt_store,
+        missing_pos).  A bad image raises ChunkerError and changes nothing."""
+        if isinstance(image, (str, os.PathLike)):
+            with open(image, "rb") as f:
+                image = f.read()
+        image = bytes(image)
+        if store is None:
+            raise ValueError("store=(blobs, offsets) is required")
+        blobs, offsets = store
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+        if off.size != self.m + 1:
+            raise ValueError(f"the listing has {self.m} entries: {off.size} offsets")
+        if self.device:
+            ptr = ctypes.c_void_p(int(blobs) or None)
+        else:
+            keep = _as_u8(blobs)
+            ptr = _ptr(keep)
+        isz = icsum = None
+        if info is not None:
+            if info[0] is not None:
+                isz = ctypes.byref(ctypes.c_uint64(int(info[0])))
+            if info[1] is not None:
+                if len(bytes(info[1])) != 32:
+                    raise ValueError("a checksum has 32 bytes")
+                icsum = ctypes.create_string_buffer(bytes(info[1]), 32)
+        cs, mp = self._lists(_index_digest_span(image)[2])
+        res, nc, nm = VerifyResult(), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        name = "pbs_verify_index_device" if self.device else "pbs_verify_index_host"
+        rc = getattr(lib(), name)(self._h, image, len(image), verify_crypt_mode(crypt_mode), isz, icsum, ptr,
+                                  off.ctypes.data, int(budget), ctypes.byref(res), cs.ctypes.data, cs.size,
+                                  ctypes.byref(nc), mp.ctypes.data, mp.size, ctypes.byref(nm))
+        if rc != PBS_OK:
+            raise ChunkerError(rc, name)
+        return res.as_dict(), cs[:min(cs.size, nc.value)].copy(), mp[:min(mp.size, nm.value)].copy()
+
+
+def _manifest_of(snapshot_dir):
+    """``BackupDir::load_manifest``: index.json.blob through the blob decoder, then JSON."""
+    import json
+
+    with open(os.path.join(snapshot_dir, "index.json.blob"), "rb") as f:
+        raw = f.read()
+    payload, kind, status = blob_decode_host(raw)
+    if status != BLOB_ST_OK:
+        raise ValueError(f"manifest blob: status {status}")
+    if kind == BLOB_KIND_COMPRESSED:
+        cap = 1 << 20
+        while True:
+            data, zst = zstd_inflate_host(payload, cap)
+            if zst == ZST_TOO_LARGE and cap < (128 << 20):
+                cap *= 4
+                continue
+            if zst != ZST_OK:
+                raise ValueError(f"manifest blob: zstd status {zst}")
+            payload = data
+            break
+    manifest = json.loads(payload.decode("utf-8"))
+    if not isinstance(manifest.get("files"), list):
+        raise ValueError("manifest without files")
+    return manifest
+
+
+def verify_snapshot(base, snapshot_dir, worker: VerifyWorker, rename: bool = False, batch_bytes: int = 256 << 20):
+    """``verify_backup_dir_with_lock`` (src/backup/verify.rs:364-446) for the snapshot directory
+    ``snapshot_dir`` of the datastore under ``base``, with ``worker`` (over
+    ``list_chunk_store(base)``) carrying the chunk states from snapshot to snapshot.  Walks the
+    manifest's files as :404-432 does: a .blob through ``verify_blob``; a .fidx / .didx through
+    the size and checksum check, the plan, the todo chunk files read from ``base/.chunks`` in
+    batches of about ``batch_bytes`` (a file that cannot be read is a load failure), and the
+    finish.  With ``rename`` the chunks found corrupt are moved to ``bad_chunk_path`` (:72-106).
+    Returns ("ok" | "failed", [(filename, None | error text, result dict | None)]).  A manifest
+    that does not load is ("failed", []).  Not done here: writing verify_state back into the
+    manifest, snapshot locks, namespaces and group walking, the filter callback, the task log."""
+    if worker.paths is None:
+        raise ValueError("the worker's listing has no paths")
+    try:
+        manifest = _manifest_of(snapshot_dir)
+    except (OSError, ValueError, ChunkerError):
+        return "failed", []
+    results = []
+    for info in manifest["files"]:
+        name = str(info.get("filename", ""))
+        res = None
+        try:
+            size, csum = int(info["size"]), bytes.fromhex(info["csum"])
+            path = os.path.join(snapshot_dir, name)
+            if name.endswith(".blob"):
+                with open(path, "rb") as f:
+                    raw = f.read()
+                v = verify_blob(raw, (size, csum))
+                err = _VERIFY_BLOB_ERRORS[v] or None
+            elif name.endswith(".fidx") or name.endswith(".didx"):
+                mode = verify_crypt_mode(info.get("crypt-mode", "none"))
+                err, res = _verify_index_files(worker, path, name.endswith(".fidx"), mode, size, csum, rename,
+                                               batch_bytes)
+            else:
+                err = f"unable to parse archive type of {name!r}"
+        except (OSError, ValueError, KeyError, ChunkerError) as e:
+            try:
+                worker.abort_index()
+            except ChunkerError:
+                pass
+            err = str(e) or type(e).__name__
+        results.append((name, err, res))
+    return ("ok" if all(e is None for _, e, _ in results) else "failed"), results
+
+
+def _verify_index_files(worker, path, fixed, mode, info_size, info_csum, rename, batch_bytes):
+    """verify_fixed_index / verify_dynamic_index (:272-314) + verify_index_chunks with the chunk
+    files read from disk: (None | error text, result dict | None)."""
+    if fixed:
+        r = FixedIndexReader(path)
+        n = r.index_count()
+        sizes = np.minimum(np.uint64(r.chunk_size), np.uint64(r.size) - np.arange(n, dtype=np.uint64) * np.uint64(r.chunk_size))
+    else:
+        r = DynamicIndexReader(path)
+        n = r.index_count()
+        sizes = np.diff(np.concatenate([[0], r.ends]).astype(np.uint64))
+    if r.index_bytes() != info_size:
+        return f"wrong size ({info_size} != {r.index_bytes()})", None
+    if r.compute_csum()[0] != info_csum:
+        return "wrong index checksum", None
+    todo_store, _ = worker.plan(r.digests, sizes, mode)
+    t = 0
+    while t < todo_store.size:
+        parts, offs, failed = [], [0], []
+        while t < todo_store.size and (not parts or offs[-1] < batch_bytes):
+            try:
+                with open(worker.paths[int(todo_store[t])], "rb") as f:
+                    data = f.read()
+                failed.append(0)
+            except OSError:
+                data = b""
+                failed.append(1)
+            parts.append(data)
+            offs.append(offs[-1] + len(data))
+            t += 1
+        raw = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        if worker.device:
+            import torch
+
+            dev = torch.from_numpy(raw.copy()).to("cuda") if raw.size else None
+            worker.submit(dev.data_ptr() if dev is not None else 0, offs, failed)
+        else:
+            worker.submit(raw, offs, failed)
+    res, corrupt, _ = worker.finish(n)
+    if rename:
+        for j in corrupt:
+            p = worker.paths[int(j)]
+            try:
+                os.rename(p, bad_chunk_path(p))
+            except FileNotFoundError:
+                pass  # (:96)
+    return (None if res["ok"] else "chunks could not be verified"), res

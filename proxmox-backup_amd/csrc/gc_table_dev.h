@@ -1,5 +1,5 @@
-// The device side of the store table that garbage collection (pbs_gc.hip) and the verify job
-// (pbs_verify.hip) share: the chunk store's listing as an open-addressing table of u32 store
+// The device side of the store table that garbage collection (pbs_gc.hip), the verify job
+// (pbs_verify.hip) and the sync job (pbs_sync.hip, which also inserts into it) share: the chunk store's listing as an open-addressing table of u32 store
 // positions (capacity 2^L >= max(2 m, 64), home slot pbs_gc_home_slot, linear probing with
 // wrap-around; gc_common.h has the size rule and the hash constant).  Device code: include it
 // from a .hip file only.  Everything is in an unnamed namespace, so each translation unit gets

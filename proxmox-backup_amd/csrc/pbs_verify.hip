@@ -26,6 +26,7 @@
 #include "pbs_restore.h"
 #include "pbs_verify.h"
 #include "verify_common.h"
+#include "verify_dev.h"
 
 struct pbs_verify {
     int dev = 0, ncu = 0;
@@ -48,17 +49,6 @@ namespace {
 using namespace pbs::gc;
 
 enum VCtr : int { kSkipVerified, kSkipCorrupt, kFailing, kVCtrs };
-
-// the block's sum of one flag per lane into out (thread 0), by ballots; all threads call it
-__device__ __forceinline__ uint32_t block_count(bool flag, uint32_t* wcnt) {
-    const unsigned long long b = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t c = 0;
-    for (int w = 0; w < kGcWaves; ++w) c += wcnt[w];
-    __syncthreads();  // (wcnt is written again by the next call)
-    return c;
-}
 
 // One lane per index entry: walks the cluster from the home slot to the first free slot and keeps
 // the LOWEST store position with the entry's digest (equal digests sit in slots of their own).
@@ -142,23 +132,7 @@ __global__ __launch_bounds__(kGcThreads) void verify_compact_kernel(const uint8_
     }
 }
 
-// One lane per submitted blob: is its magic one of the two encrypted ones?  spans[2 t] is the
-// blob's start in `blobs`, spans[2 t + 1] its length; a blob under a header has no magic.
-__global__ __launch_bounds__(kGcThreads) void verify_magic_kernel(const uint8_t* __restrict__ blobs,
-                                                                  const uint64_t* __restrict__ spans, uint64_t k,
-                                                                  uint8_t* __restrict__ enc) {
-    const uint64_t t = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
-    if (t >= k) return;
-    uint8_t e = 0;
-    if (spans[2 * t + 1] >= PBS_BLOB_HEADER_SIZE) {
-        const uint8_t* p = blobs + spans[2 * t];
-        uint64_t v = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) v |= (uint64_t)p[b] << (8 * b);  // (a blob starts at any alignment)
-        e = v == kEncMagicLe || v == kEncComprMagicLe;
-    }
-    enc[t] = e;
-}
+// (verify_magic_kernel, the magic read of a submit: verify_dev.h)
 
 // One lane per submitted blob, scattered by store position (the plan names every position once).
 __global__ __launch_bounds__(kGcThreads) void verify_state_kernel(const uint32_t* __restrict__ store_pos,

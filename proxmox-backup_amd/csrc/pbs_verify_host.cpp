@@ -250,6 +250,10 @@ int plan(pbs_verify_host* h, const uint8_t* digests, const uint64_t* sizes, size
 
 }  // namespace
 
+uint8_t pbs::verify::host_blob_verdict(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind) {
+    return decode_one(len ? p : kMagics[0], len, want, size, kind);
+}
+
 extern "C" int pbs_verify_begin_host(const uint8_t* store_digests, size_t m, pbs_verify_host** out, double* build_ms) {
     const Clock::time_point t0 = Clock::now();
     if (out) *out = nullptr;

@@ -166,6 +166,13 @@ inline void index_entries(const uint8_t* image, const gc::IndexLayout& lo, std::
     }
 }
 
+// pbs_verify_host.cpp: the host mirror's verdict on one blob image (p may be NULL with len == 0)
+// with no config, the digest `want` and a slot of exactly `size` bytes -- what
+// pbs_blob_decode_inflate_device reports for it (an encrypted blob that loads: NO_CONFIG).
+// *kind: PBS_BLOB_KIND_*.  Throws std::bad_alloc when there is no memory for the slot.  Shared
+// with the sync job's mirror (pbs_sync_host.cpp).
+uint8_t host_blob_verdict(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind);
+
 // The next batch of the whole-index call: plan items [t0, t1), t1 > t0, such that the blobs plus
 // the output slots of the unencrypted ones stay at or below `budget` (0: no bound) -- but one
 // blob always goes.  blob_len(t) and enc[t] describe plan item t.

@@ -42,6 +42,7 @@
 #include "pbs_fixed.h"
 #include "pbs_gc.h"
 #include "pbs_verify.h"
+#include "pbs_sync.h"
 
 namespace pbs {
 
@@ -986,6 +987,133 @@ class VerifyWorker {
     bool device_;
     pbs_verify* dev_ = nullptr;
     pbs_verify_host* host_ = nullptr;
+};
+
+// The sync job's worker (include/pbs_sync.h) over the local chunk store's listing (32 bytes of
+// digest per chunk file): the store as it grows, and the claims of the current group.
+// device == true: table, digest list, present and claimed bytes live in the memory of hip_stream's
+// device and the blobs handed to submit are device memory; false: the host mirror.
+class SyncWorker {
+  public:
+    struct Plan {
+        uint32_t index_check = PBS_VERIFY_INDEX_OK;  // of plan_index; not OK: nothing was claimed, no index is open
+        std::vector<uint8_t> verdict;                // PBS_SYNC_DUP / EXISTS / FETCH per entry
+        std::vector<uint32_t> fetch_store, fetch_entry, touch_store;
+    };
+    struct Listing {
+        std::vector<uint8_t> digests, present;  // 32 and 1 per entry
+    };
+
+    explicit SyncWorker(const std::vector<uint8_t>& digests, size_t reserve = 0, bool device = true,
+                        void* hip_stream = nullptr)
+        : device_(device) {
+        const size_t m = digests.size() / 32;
+        if (digests.size() != 32 * m) throw std::invalid_argument("32 bytes of digest per entry");
+        const int rc = device_ ? pbs_sync_begin(digests.data(), m, reserve, &dev_, &build_ms, hip_stream)
+                               : pbs_sync_begin_host(digests.data(), m, reserve, &host_, &build_ms);
+        check(rc, "pbs_sync_begin");
+    }
+    ~SyncWorker() { close(); }
+    SyncWorker(const SyncWorker&) = delete;
+    SyncWorker& operator=(const SyncWorker&) = delete;
+
+    double build_ms = 0, plan_ms = 0;  // of the last such call
+    pbs_sync_timing timing{};          // of the last submit
+
+    void close() {
+        if (dev_) pbs_sync_end(dev_);
+        if (host_) pbs_sync_end_host(host_);
+        dev_ = nullptr;
+        host_ = nullptr;
+    }
+    size_t count() { return device_ ? pbs_sync_count(dev_) : pbs_sync_count_host(host_); }
+    uint32_t table_log2() { return device_ ? pbs_sync_table_log2(dev_) : pbs_sync_table_log2_host(host_); }
+    Listing listing() {
+        Listing l;
+        const size_t c = count();
+        l.digests.resize(32 * c);
+        l.present.resize(c);
+        check(device_ ? pbs_sync_listing(dev_, l.digests.data(), l.present.data(), c, nullptr)
+                      : pbs_sync_listing_host(host_, l.digests.data(), l.present.data(), c, nullptr),
+              "pbs_sync_listing");
+        return l;
+    }
+    // A fresh downloaded_chunks: the next group.
+    void new_group() { check(device_ ? pbs_sync_new_group(dev_) : pbs_sync_new_group_host(host_), "pbs_sync_new_group"); }
+    // The verdicts and the two lists for an index of n entries (digests: 32 n bytes, sizes: n).
+    Plan plan(const std::vector<uint8_t>& digests, const std::vector<uint64_t>& sizes) {
+        const size_t n = sizes.size();
+        if (digests.size() != 32 * n) throw std::invalid_argument("32 bytes of digest per size");
+        Plan p;
+        p.verdict.resize(n);
+        p.fetch_store.resize(n);
+        p.fetch_entry.resize(n);
+        p.touch_store.resize(n);
+        size_t nf = 0, nt = 0;
+        const int rc = device_ ? pbs_sync_plan(dev_, digests.data(), sizes.data(), n, p.verdict.data(), p.fetch_store.data(),
+                                               p.fetch_entry.data(), n, &nf, p.touch_store.data(), n, &nt, &plan_ms)
+                               : pbs_sync_plan_host(host_, digests.data(), sizes.data(), n, p.verdict.data(),
+                                                    p.fetch_store.data(), p.fetch_entry.data(), n, &nf,
+                                                    p.touch_store.data(), n, &nt, &plan_ms);
+        check(rc, "pbs_sync_plan");
+        p.fetch_store.resize(nf);
+        p.fetch_entry.resize(nf);
+        p.touch_store.resize(nt);
+        return p;
+    }
+    // The same for a .didx / .fidx image, after verify_archive against the manifest's FileInfo
+    // (info_size / info_csum, or nullptr).
+    Plan plan_index(const uint8_t* image, size_t len, const uint64_t* info_size, const uint8_t* info_csum) {
+        const size_t cap = len > 4096 ? (len - 4096) / 32 : 0;
+        Plan p;
+        p.verdict.resize(cap);
+        p.fetch_store.resize(cap);
+        p.fetch_entry.resize(cap);
+        p.touch_store.resize(cap);
+        size_t n = 0, nf = 0, nt = 0;
+        const int rc =
+            device_ ? pbs_sync_index_image(dev_, image, len, info_size, info_csum, &p.index_check, &n, p.verdict.data(), cap,
+                                           p.fetch_store.data(), p.fetch_entry.data(), cap, &nf, p.touch_store.data(), cap,
+                                           &nt, &plan_ms)
+                    : pbs_sync_index_image_host(host_, image, len, info_size, info_csum, &p.index_check, &n,
+                                                p.verdict.data(), cap, p.fetch_store.data(), p.fetch_entry.data(), cap, &nf,
+                                                p.touch_store.data(), cap, &nt, &plan_ms);
+        check(rc, "pbs_sync_index_image");
+        p.verdict.resize(p.index_check == PBS_VERIFY_INDEX_OK ? n : 0);
+        p.fetch_store.resize(nf);
+        p.fetch_entry.resize(nf);
+        p.touch_store.resize(nt);
+        return p;
+    }
+    // The next blob_offsets.size() - 1 fetch items as raw blob images; returns their status codes.
+    std::vector<uint8_t> submit(const uint8_t* blobs, const std::vector<uint64_t>& blob_offsets,
+                                const uint8_t* load_failed = nullptr, std::vector<uint8_t>* kinds = nullptr) {
+        const size_t k = blob_offsets.empty() ? 0 : blob_offsets.size() - 1;
+        std::vector<uint8_t> status(k), kd(k);
+        const int rc = device_ ? pbs_sync_submit(dev_, blobs, blob_offsets.data(), load_failed, k, kd.data(), status.data(),
+                                                 &timing)
+                               : pbs_sync_submit_host(host_, blobs, blob_offsets.data(), load_failed, k, kd.data(),
+                                                      status.data(), &timing);
+        check(rc, "pbs_sync_submit");
+        if (kinds) *kinds = kd;
+        return status;
+    }
+    pbs_sync_result finish() {
+        pbs_sync_result r;
+        check(device_ ? pbs_sync_finish(dev_, &r) : pbs_sync_finish_host(host_, &r), "pbs_sync_finish");
+        return r;
+    }
+    void abort_index() {
+        check(device_ ? pbs_sync_abort_index(dev_) : pbs_sync_abort_index_host(host_), "pbs_sync_abort_index");
+    }
+
+  private:
+    static void check(int rc, const char* what) {
+        if (rc != PBS_OK) throw std::runtime_error(std::string(what) + ": " + pbs_strerror(rc));
+    }
+    bool device_;
+    pbs_sync* dev_ = nullptr;
+    pbs_sync_host* host_ = nullptr;
 };
 
 }  // namespace pbs

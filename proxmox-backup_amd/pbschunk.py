@@ -94,6 +94,13 @@ EXPORTED_SYMBOLS = (
     "pbs_verify_blob_host", "pbs_verify_begin_host", "pbs_verify_states_host", "pbs_verify_end_host",
     "pbs_verify_plan_host", "pbs_verify_abort_index_host", "pbs_verify_submit_host", "pbs_verify_finish_host",
     "pbs_verify_index_host",
+    # the sync job (include/pbs_sync.h)
+    "pbs_sync_begin", "pbs_sync_count", "pbs_sync_table_log2", "pbs_sync_listing", "pbs_sync_new_group",
+    "pbs_sync_end", "pbs_sync_release", "pbs_sync_plan", "pbs_sync_lists", "pbs_sync_submit", "pbs_sync_finish",
+    "pbs_sync_abort_index", "pbs_sync_index_image",
+    "pbs_sync_begin_host", "pbs_sync_count_host", "pbs_sync_table_log2_host", "pbs_sync_listing_host",
+    "pbs_sync_new_group_host", "pbs_sync_end_host", "pbs_sync_plan_host", "pbs_sync_lists_host",
+    "pbs_sync_submit_host", "pbs_sync_finish_host", "pbs_sync_abort_index_host", "pbs_sync_index_image_host",
 )
 
 
@@ -265,6 +272,16 @@ class VerifyTiming(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SyncResult(ctypes.Structure):
+    """pbs_sync_result: the counts of one pulled index."""
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "entries", "dup", "exists", "fetch", "appended", "inserted", "failed", "load_failed", "chunk_count",
+        "bytes", "first_failed")] + [("ok", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
 class HybridOpts(ctypes.Structure):
@@ -442,6 +459,7 @@ def lib():
                                     ctypes.POINTER(sz)], i),
         "pbs_verify_index_host": ([p, p, sz, i, ctypes.POINTER(u64), p, p, p, sz, ctypes.POINTER(VerifyResult),
                                    p, sz, ctypes.POINTER(sz), p, sz, ctypes.POINTER(sz)], i),
+        "pbs_sync_release": ([], None),
         "pbs_blob_encode_release": ([], None),
         "pbs_digest_hybrid_release": ([], None),
         "pbs_pipeline_release": ([], None),
@@ -452,6 +470,23 @@ def lib():
         "pbs_test_handle_stats": ([p, ctypes.POINTER(u64)], i),
         "pbs_test_gcm_tag_segments_host": ([p, p, p, sz, p], i),
     }
+    psz = ctypes.POINTER(sz)
+    for sfx, tail in (("", [p]), ("_host", [])):  # (the device calls and the mirror's: the same but for the stream)
+        sig.update({
+            "pbs_sync_begin" + sfx: ([p, sz, sz, ctypes.POINTER(p), dbl] + tail, i),
+            "pbs_sync_count" + sfx: ([p], sz),
+            "pbs_sync_table_log2" + sfx: ([p], ctypes.c_uint32),
+            "pbs_sync_listing" + sfx: ([p, p, p, sz, psz], i),
+            "pbs_sync_new_group" + sfx: ([p], i),
+            "pbs_sync_end" + sfx: ([p], None),
+            "pbs_sync_plan" + sfx: ([p, p, p, sz, p, p, p, sz, psz, p, sz, psz, dbl], i),
+            "pbs_sync_lists" + sfx: ([p, p, p, sz, psz, p, sz, psz], i),
+            "pbs_sync_submit" + sfx: ([p, p, p, p, sz, p, p, ctypes.POINTER(VerifyTiming)], i),
+            "pbs_sync_finish" + sfx: ([p, ctypes.POINTER(SyncResult)], i),
+            "pbs_sync_abort_index" + sfx: ([p], i),
+            "pbs_sync_index_image" + sfx: ([p, p, sz, ctypes.POINTER(u64), p, ctypes.POINTER(ctypes.c_uint32), psz, p, sz,
+                                            p, p, sz, psz, p, sz, psz, dbl], i),
+        })
     for name, (args, res) in sig.items():
         if os.environ.get("PBS_LIBPBSCHUNK_AB") and not hasattr(L, name):
             continue  # (an older build in an A/B run: the symbols it has)
@@ -2655,3 +2690,448 @@ def _verify_index_files(worker, path, fixed, mode, info_size, info_csum, rename,
             except FileNotFoundError:
                 pass  # (:96)
     return (None if res["ok"] else "chunks could not be verified"), res
+
+
+# ---- the sync job (include/pbs_sync.h) -----------------------------------------------------------
+
+SYNC_DUP, SYNC_EXISTS, SYNC_FETCH = 0, 1, 2
+SYNC_ST_LOAD_FAILED = 32          # PBS_SYNC_ST_LOAD_FAILED: the caller could not fetch the blob
+SYNC_NONE = (1 << 64) - 1         # PBS_SYNC_NONE: first_failed of a result with no failing item
+_ENC_MAGICS = (bytes([123, 103, 133, 190, 34, 45, 76, 240]), bytes([230, 89, 27, 191, 11, 191, 216, 11]))
+
+
+def sync_release() -> None:
+    """pbs_sync_release: free the idle work areas of the sync calls."""
+    lib().pbs_sync_release()
+
+
+def chunk_path(base, digest) -> str:
+    """``ChunkStore::chunk_path`` (pbs-datastore/src/chunk_store.rs:557-570):
+    base/.chunks/<first four hex digits>/<hex>."""
+    h = bytes(digest).hex()
+    return os.path.join(base, ".chunks", h[:4], h)
+
+
+def _index_entries(image: bytes, n: int):
+    """(digests (n, 32), chunk_info sizes (n)) of an accepted .didx / .fidx image."""
+    off, stride, _ = _index_digest_span(image)
+    head = off - (stride - 32)
+    rows = np.frombuffer(image, dtype=np.uint8, count=n * stride, offset=head).reshape(n, stride)
+    digests = np.ascontiguousarray(rows[:, stride - 32:])
+    if stride == 32:
+        size, cs = (int.from_bytes(image[o:o + 8], "little") for o in (64, 72))
+        sizes = np.minimum(np.uint64(cs), np.uint64(size) - np.arange(n, dtype=np.uint64) * np.uint64(cs))
+    else:
+        ends = np.ascontiguousarray(rows[:, :8]).view("<u8").reshape(-1)
+        sizes = np.diff(np.concatenate([[0], ends]).astype(np.uint64))
+    return digests, sizes.astype(np.uint64)
+
+
+class SyncWorker:
+    """The target side of a sync job (``pull_index_chunks``, src/server/pull.rs:605-705) over the
+    local chunk store's listing (``list_chunk_store``'s result, or (paths or None, digests[,
+    flags]); entries whose flags are not 0 are dropped): a context manager over a pbs_sync handle
+    (``device=True``: table, digest list, present and claimed bytes live in the memory of
+    ``hip_stream``'s device) or over the host mirror's (``device=False``: no GPU).  ``reserve``:
+    the number of chunks the job is expected to add; with enough of it the table is never rebuilt.
+    The claimed bytes -- ``downloaded_chunks`` -- live until ``new_group``, everything else until
+    ``close``."""
+
+    def __init__(self, listing, reserve: int = 0, device: bool = True, hip_stream: int = 0):
+        digests = _digest_rows(listing[1])
+        if len(listing) > 2 and listing[2] is not None:
+            keep = np.flatnonzero(np.asarray(listing[2], dtype=np.uint8).reshape(-1) == 0)
+            digests = np.ascontiguousarray(digests[keep])
+        m = int(digests.shape[0])
+        self.device = bool(device)
+        self.hip_stream = int(hip_stream)
+        self._sfx = "" if self.device else "_host"
+        h, ms = ctypes.c_void_p(None), ctypes.c_double(0)
+        args = [digests.ctypes.data if m else None, m, int(reserve), ctypes.byref(h), ctypes.byref(ms)]
+        if self.device:
+            rc = lib().pbs_sync_begin(*args, ctypes.c_void_p(hip_stream))
+        else:
+            rc = lib().pbs_sync_begin_host(*args)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_sync_begin" + self._sfx)
+        self._h = h
+        self.build_ms = float(ms.value)
+        self.plan_ms = 0.0          # of the last plan
+        self.timing = None          # of the last submit
+        self.index_digests = None   # of the open index: (n, 32)
+        self.index_sizes = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self) -> None:
+        """pbs_sync_end.  Every later call raises ChunkerError(PBS_ERR_INVALID)."""
+        if getattr(self, "_h", None) is not None and not getattr(self, "_closed", False):
+            self._closed = True
+            (lib().pbs_sync_end if self.device else lib().pbs_sync_end_host)(self._h)
+
+    def _fn(self, name: str):
+        return getattr(lib(), name + self._sfx)
+
+    def _check(self, rc: int, name: str) -> None:
+        if rc != PBS_OK:
+            raise ChunkerError(rc, name + self._sfx)
+
+    @property
+    def count(self) -> int:
+        """pbs_sync_count: the entries, listed and appended (0 after ``close``)."""
+        return int(self._fn("pbs_sync_count")(self._h))
+
+    @property
+    def table_log2(self) -> int:
+        """pbs_sync_table_log2."""
+        return int(self._fn("pbs_sync_table_log2")(self._h))
+
+    def listing(self):
+        """pbs_sync_listing: (digests (count, 32), present (count)) as they stand."""
+        n = ctypes.c_size_t(0)
+        self._check(self._fn("pbs_sync_listing")(self._h, None, None, 0, ctypes.byref(n)), "pbs_sync_listing")
+        d, p = np.zeros((n.value, 32), dtype=np.uint8), np.zeros(n.value, dtype=np.uint8)
+        self._check(self._fn("pbs_sync_listing")(self._h, _ptr(d), _ptr(p), n.value, ctypes.byref(n)), "pbs_sync_listing")
+        return d, p
+
+    def new_group(self) -> None:
+        """pbs_sync_new_group: a fresh ``downloaded_chunks`` (pull.rs:1134)."""
+        self._check(self._fn("pbs_sync_new_group")(self._h), "pbs_sync_new_group")
+
+    def plan(self, digests, sizes):
+        """pbs_sync_plan over an index's digests (n, 32) and chunk sizes (n): (verdict (n) of
+        SYNC_DUP / SYNC_EXISTS / SYNC_FETCH, fetch_store, fetch_entry, touch_store)."""
+        d = _digest_rows(digests)
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint64).reshape(-1))
+        n = int(d.shape[0])
+        if sz.size != n:
+            raise ValueError(f"{n} digests, {sz.size} sizes")
+        v = np.zeros(n, dtype=np.uint8)
+        fs, fe, ts = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        nf, nt, ms = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_double(0)
+        rc = self._fn("pbs_sync_plan")(self._h, _ptr(d), _ptr(sz), n, _ptr(v), _ptr(fs), _ptr(fe), n, ctypes.byref(nf),
+                                       _ptr(ts), n, ctypes.byref(nt), ctypes.byref(ms))
+        self._check(rc, "pbs_sync_plan")
+        self.plan_ms = float(ms.value)
+        self.index_digests, self.index_sizes = d, sz
+        return v, fs[:nf.value], fe[:nf.value], ts[:nt.value]
+
+    def lists(self):
+        """pbs_sync_lists: (fetch_store, fetch_entry, touch_store) of the open index again."""
+        nf, nt = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        self._check(self._fn("pbs_sync_lists")(self._h, None, None, 0, ctypes.byref(nf), None, 0, ctypes.byref(nt)),
+                    "pbs_sync_lists")
+        fs, fe, ts = np.zeros(nf.value, np.uint32), np.zeros(nf.value, np.uint32), np.zeros(nt.value, np.uint32)
+        rc = self._fn("pbs_sync_lists")(self._h, _ptr(fs), _ptr(fe), fs.size, ctypes.byref(nf), _ptr(ts), ts.size,
+                                        ctypes.byref(nt))
+        self._check(rc, "pbs_sync_lists")
+        return fs, fe, ts
+
+    def plan_index(self, image, info=None):
+        """pbs_sync_index_image over a .didx / .fidx image (bytes or a path).  ``info``: None or
+        (size, csum) of the manifest's FileInfo, either of which may be None.  Returns
+        (index_check, verdict, fetch_store, fetch_entry, touch_store); with index_check
+        VERIFY_INDEX_WRONG_SIZE / WRONG_CSUM nothing was claimed, no index is open and the lists
+        are empty.  A bad image raises ChunkerError and changes nothing."""
+        if isinstance(image, (str, os.PathLike)):
+            with open(image, "rb") as f:
+                image = f.read()
+        image = bytes(image)
+        isz = icsum = None
+        if info is not None:
+            if info[0] is not None:
+                isz = ctypes.byref(ctypes.c_uint64(int(info[0])))
+            if info[1] is not None:
+                if len(bytes(info[1])) != 32:
+                    raise ValueError("a checksum has 32 bytes")
+                icsum = ctypes.create_string_buffer(bytes(info[1]), 32)
+        cap = _index_digest_span(image)[2]
+        v = np.zeros(cap, dtype=np.uint8)
+        fs, fe, ts = (np.zeros(cap, dtype=np.uint32) for _ in range(3))
+        chk, n = ctypes.c_uint32(0), ctypes.c_size_t(0)
+        nf, nt, ms = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_double(0)
+        rc = self._fn("pbs_sync_index_image")(self._h, image, len(image), isz, icsum, ctypes.byref(chk), ctypes.byref(n),
+                                              _ptr(v), cap, _ptr(fs), _ptr(fe), cap, ctypes.byref(nf), _ptr(ts), cap,
+                                              ctypes.byref(nt), ctypes.byref(ms))
+        self._check(rc, "pbs_sync_index_image")
+        self.plan_ms = float(ms.value)
+        if chk.value != VERIFY_INDEX_OK:
+            return int(chk.value), v[:0], fs[:0], fe[:0], ts[:0]
+        self.index_digests, self.index_sizes = _index_entries(image, n.value)
+        return 0, v[:n.value], fs[:nf.value], fe[:nf.value], ts[:nt.value]
+
+    def submit(self, blobs, blob_offsets, load_failed=None):
+        """pbs_sync_submit of the next k fetch items.  ``blobs``: for a device handle the device
+        address of the raw blob images, for the mirror bytes or an array; ``blob_offsets``: k + 1
+        offsets into it; ``load_failed``: None or k flags.  Returns (kinds (k), status (k))."""
+        off = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64).reshape(-1))
+        k = max(0, off.size - 1)
+        lf = None
+        if load_failed is not None:
+            lf = np.ascontiguousarray(np.asarray(load_failed, dtype=np.uint8).reshape(-1))
+            if lf.size != k:
+                raise ValueError(f"{k} blobs, {lf.size} load_failed flags")
+        if self.device:
+            ptr = ctypes.c_void_p(int(blobs) or None)
+        else:
+            keep = _as_u8(blobs)
+            ptr = _ptr(keep)
+        kinds, status = np.zeros(k, dtype=np.uint8), np.zeros(k, dtype=np.uint8)
+        t = VerifyTiming()
+        rc = self._fn("pbs_sync_submit")(self._h, ptr, off.ctypes.data if off.size else None,
+                                         None if lf is None else _ptr(lf), k, _ptr(kinds), _ptr(status), ctypes.byref(t))
+        self._check(rc, "pbs_sync_submit")
+        self.timing = t.as_dict()
+        return kinds, status
+
+    def finish(self) -> dict:
+        """pbs_sync_finish: the result dict (pbs_sync_result; first_failed SYNC_NONE when no item failed)."""
+        res = SyncResult()
+        self._check(self._fn("pbs_sync_finish")(self._h, ctypes.byref(res)), "pbs_sync_finish")
+        return res.as_dict()
+
+    def abort_index(self) -> None:
+        """pbs_sync_abort_index: drop the rest of the plan; claims and appended entries stay."""
+        self._check(self._fn("pbs_sync_abort_index")(self._h), "pbs_sync_abort_index")
+
+    def pull_index(self, image, info, remote, budget: int = 0):
+        """One index from a source store that is resident (a local-to-local sync): ``remote`` is
+        (digests (M, 32), blobs, offsets (M + 1)), the source's chunk files back to back -- for a
+        device handle a device address, for the mirror bytes or an array.  ``plan_index``, then
+        the fetch digests are looked up in the remote listing (``digest_lookup_device`` /
+        ``digest_lookup_host``; a digest the source lacks is a load failure), packed in batches
+        (``copy_segments_device``) whose blobs plus unencrypted output slots stay at or below
+        ``budget`` bytes (0: no bound; one blob always goes) and submitted until the plan is
+        drained, then ``finish``.  Returns (index_check, result dict or None, dict(verdict,
+        fetch_store, fetch_entry, touch_store, kinds, status))."""
+        chk, verdict, fs, fe, ts = self.plan_index(image, info)
+        out = dict(verdict=verdict, fetch_store=fs, fetch_entry=fe, touch_store=ts, kinds=np.zeros(0, np.uint8),
+                   status=np.zeros(0, np.uint8))
+        if chk != VERIFY_INDEX_OK:
+            return chk, None, out
+        try:
+            out["kinds"], out["status"] = self._pull_fetch_list(fe, remote, int(budget))
+        except Exception:
+            self.abort_index()
+            raise
+        return 0, self.finish(), out
+
+    def _pull_fetch_list(self, fe, remote, budget):
+        rdig, rblobs, roff = _digest_rows(remote[0]), remote[1], np.asarray(remote[2], dtype=np.uint64).reshape(-1)
+        M, k = int(rdig.shape[0]), int(fe.size)
+        if roff.size != M + 1:
+            raise ValueError(f"the remote listing has {M} entries: {roff.size} offsets")
+        if k == 0:
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+        want = np.ascontiguousarray(self.index_digests[fe])
+        sizes = self.index_sizes[fe]
+        torch = None
+        if self.device:
+            import torch
+
+            t_want, t_rem = torch.from_numpy(want).cuda(), torch.from_numpy(np.ascontiguousarray(rdig)).cuda()
+            t_pos, t_first = (torch.empty(k, dtype=torch.int32, device="cuda") for _ in range(2))
+            torch.cuda.synchronize()
+            digest_lookup_device(t_want.data_ptr(), k, t_rem.data_ptr() if M else 0, M, t_pos.data_ptr(),
+                                 t_first.data_ptr(), self.hip_stream)
+            pos = t_pos.cpu().numpy().view(np.uint32)
+        else:
+            rblobs = _as_u8(rblobs)
+            pos = digest_lookup_host(want, rdig)[0]
+        lf = (pos == LOOKUP_MISSING).astype(np.uint8)
+        at = np.where(lf, 0, pos).astype(np.int64)
+        src = np.where(lf, 0, roff[at] if M else 0).astype(np.uint64)
+        lens = np.where(lf, 0, (roff[at + 1] - roff[at]) if M else 0).astype(np.uint64)
+        # the magic read of every blob: an encrypted one takes no output slot in its batch
+        hl = np.minimum(lens, 8)
+        ho = np.arange(k, dtype=np.uint64) * np.uint64(8)
+        if self.device:
+            t_heads = torch.zeros(8 * k, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            copy_segments_device(int(rblobs), t_heads.data_ptr(), src, ho, hl, self.hip_stream)
+            heads = t_heads.cpu().numpy()
+        else:
+            heads = np.zeros(8 * k, dtype=np.uint8)
+            for t in range(k):
+                heads[8 * t:8 * t + int(hl[t])] = rblobs[int(src[t]):int(src[t]) + int(hl[t])]
+        enc = np.array([lens[t] >= 12 and heads[8 * t:8 * t + 8].tobytes() in _ENC_MAGICS for t in range(k)])
+        need = lens + np.where(enc, 0, sizes).astype(np.uint64)
+        kinds, status = [], []
+        t0 = 0
+        while t0 < k:
+            t1, used = t0, 0
+            while t1 < k:  # (the rule of verify::batch_end)
+                nd = int(need[t1])
+                if budget and t1 > t0 and used + nd > budget:
+                    break
+                used += nd
+                t1 += 1
+            blens = lens[t0:t1]
+            offs = np.concatenate([[0], np.cumsum(blens)]).astype(np.uint64)
+            total = int(offs[-1])
+            if self.device:
+                pack = torch.empty(max(total, 1), dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                if total:
+                    copy_segments_device(int(rblobs), pack.data_ptr(), src[t0:t1], offs[:-1], blens, self.hip_stream)
+                kd, st = self.submit(pack.data_ptr(), offs, lf[t0:t1])
+            else:
+                parts = [rblobs[int(src[t]):int(src[t]) + int(lens[t])] for t in range(t0, t1)]
+                kd, st = self.submit(np.concatenate(parts + [np.zeros(1, np.uint8)]), offs, lf[t0:t1])
+            kinds.append(kd)
+            status.append(st)
+            t0 = t1
+        return np.concatenate(kinds), np.concatenate(status)
+
+
+def _write_atomic(path: str, data: bytes) -> None:
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(data)
+    os.rename(tmp, path)
+
+
+def pull_snapshot(remote_base, remote_snapshot_dir, local_base, local_snapshot_dir, worker: SyncWorker,
+                  batch_bytes: int = 256 << 20):
+    """``pull_snapshot`` / ``pull_single_archive`` (src/server/pull.rs:724-940) between two
+    datastore directories, with ``worker`` (over ``list_chunk_store(local_base)``) carrying the
+    store and ``downloaded_chunks`` from snapshot to snapshot.  The source's manifest goes to
+    ``index.json.tmp``; a local manifest with the same raw bytes means "no data changes".  Per
+    file of the manifest: a local file that already matches the manifest is skipped; otherwise the
+    source's file is copied to ``<stem>.tmp``, a .blob checked by the SHA-256 and size of its raw
+    bytes, an index by ``plan_index`` (size and checksum), its fetch list read from
+    ``remote_base/.chunks`` in batches of about ``batch_bytes`` (a file that cannot be read is a
+    load failure), submitted, and the chunks that verified written under ``local_base/.chunks``;
+    the chunks on the touch list get a new atime; the ``.tmp`` is renamed into place.  The walk
+    stops at the first file that fails (its ``.tmp`` stays behind, as the reference's does), and
+    the manifest is renamed into place only after the last file.  Returns ("ok" | "failed",
+    [(filename, None | error text, result dict | None)]).  Not done here: the client log,
+    cleanup_unreferenced_files, locks, owners, groups and namespaces, remove_vanished."""
+    def tmp_of(path):  # PathBuf::set_extension("tmp")
+        return os.path.splitext(path)[0] + ".tmp"
+
+    os.makedirs(local_snapshot_dir, exist_ok=True)
+    manifest_name = os.path.join(local_snapshot_dir, "index.json.blob")
+    try:
+        with open(os.path.join(remote_snapshot_dir, "index.json.blob"), "rb") as f:
+            raw_manifest = f.read()
+        with open(tmp_of(manifest_name), "wb") as f:
+            f.write(raw_manifest)
+        if os.path.exists(manifest_name):
+            with open(manifest_name, "rb") as f:
+                if f.read() == raw_manifest:  # "no data changes"
+                    os.unlink(tmp_of(manifest_name))
+                    return "ok", []
+        manifest = _manifest_of(remote_snapshot_dir)
+    except (OSError, ValueError, ChunkerError):
+        return "failed", []
+    results = []
+    for info in manifest["files"]:
+        name = str(info.get("filename", ""))
+        res, err = None, None
+        try:
+            size, csum = int(info["size"]), bytes.fromhex(info["csum"])
+            path = os.path.join(local_snapshot_dir, name)
+            kind = "blob" if name.endswith(".blob") else "fidx" if name.endswith(".fidx") else \
+                "didx" if name.endswith(".didx") else None
+            if kind is None:
+                raise ValueError(f"unable to parse archive type of {name!r}")
+            if os.path.exists(path):  # (:876-909)
+                if kind == "blob":
+                    with open(path, "rb") as f:
+                        raw = f.read()
+                    have = (sha256(raw), len(raw))
+                else:
+                    have = (FixedIndexReader if kind == "fidx" else DynamicIndexReader)(path).compute_csum()
+                if have == (csum, size):
+                    results.append((name, None, None))
+                    continue
+            with open(os.path.join(remote_snapshot_dir, name), "rb") as f:
+                raw = f.read()
+            tmp = tmp_of(path)
+            with open(tmp, "wb") as f:
+                f.write(raw)
+            if kind == "blob":
+                if len(raw) != size:
+                    err = f"wrong size for file '{name}' ({size} != {len(raw)})"
+                elif sha256(raw) != csum:
+                    err = f"wrong checksum for file '{name}'"
+            else:
+                err, res = _pull_index_files(worker, raw, name, size, csum, remote_base, local_base, batch_bytes)
+            if err is None:
+                os.rename(tmp, path)
+        except (OSError, ValueError, KeyError, ChunkerError) as e:
+            try:
+                worker.abort_index()
+            except ChunkerError:
+                pass
+            err = str(e) or type(e).__name__
+        results.append((name, err, res))
+        if err is not None:
+            return "failed", results
+    os.rename(tmp_of(manifest_name), manifest_name)
+    return "ok", results
+
+
+def _pull_index_files(worker, image, name, info_size, info_csum, remote_base, local_base, batch_bytes):
+    """verify_archive + pull_index_chunks with the chunk files read from and written to disk:
+    (None | error text, result dict | None)."""
+    import time
+
+    chk, _, fs, fe, ts = worker.plan_index(image, (info_size, info_csum))
+    if chk == VERIFY_INDEX_WRONG_SIZE:
+        return f"wrong size for file '{name}'", None
+    if chk == VERIFY_INDEX_WRONG_CSUM:
+        return f"wrong checksum for file '{name}'", None
+    digests = worker.index_digests
+    t = 0
+    while t < fe.size:
+        parts, offs, failed, digs = [], [0], [], []
+        while t < fe.size and (not parts or offs[-1] < batch_bytes):
+            dg = digests[int(fe[t])].tobytes()
+            try:
+                with open(chunk_path(remote_base, dg), "rb") as f:
+                    data = f.read()
+                failed.append(0)
+            except OSError:
+                data = b""
+                failed.append(1)
+            parts.append(data)
+            digs.append(dg)
+            offs.append(offs[-1] + len(data))
+            t += 1
+        raw = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        if worker.device:
+            import torch
+
+            dev = torch.from_numpy(raw.copy()).to("cuda") if raw.size else None
+            _, status = worker.submit(dev.data_ptr() if dev is not None else 0, offs, failed)
+        else:
+            _, status = worker.submit(raw, offs, failed)
+        for dg, data, st in zip(digs, parts, status):
+            if st == BLOB_ST_OK:
+                _write_atomic(chunk_path(local_base, dg), data)  # insert_chunk
+    if ts.size:
+        all_digests, _ = worker.listing()
+        for c in ts:
+            p = chunk_path(local_base, all_digests[int(c)].tobytes())
+            try:
+                st = os.lstat(p)
+                os.utime(p, ns=(time.time_ns(), st.st_mtime_ns), follow_symlinks=False)
+            except FileNotFoundError:
+                pass
+    res = worker.finish()
+    if not res["ok"]:
+        return f"sync of {name!r} failed at fetch item {res['first_failed']}", res
+    return None, res

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <vector>
 
+#include "pbs_blob.h"
 #include "pbs_chunker.h"
 
 typedef struct pbs_chunker pbs_chunker;            // include/pbs_chunker.h
@@ -153,6 +154,13 @@ hipError_t launch_crc32_spans(const uint8_t* data, const uint64_t* spans_dev, co
                               uint64_t n, uint32_t* out, hipStream_t st);
 // pbs_decode.hip: frees the idle work areas of pbs_blob_decode_device (pbs_blob_encode_release)
 void decode_release();
+// pbs_decode.hip: pbs_blob_decode_device with an internal mode for the backup session's upload
+// (pbs_backup.hip): crc_out != nullptr (n host words) takes the payloads' CRCs and the stored
+// CRC is not judged.  crc_out == nullptr is the public call.
+int decode_device_impl(const uint8_t* blobs_dev, const uint64_t* blob_offsets, size_t n, const pbs_crypt_config* cfg,
+                       const uint8_t* expect_digests, const uint64_t* expect_sizes, uint8_t* out_dev, size_t out_cap,
+                       uint64_t* out_offsets, uint8_t* kinds, uint8_t* status, ::pbs_blob_decode_timing* timing,
+                       void* hip_stream, uint32_t* crc_out);
 // pbs_inflate.hip: the zstd inflater's launch on `st` (offsets, order, lengths and status in
 // device memory; order_dev: a permutation of 0..n-1, longest frame first).  Takes 2 arena
 // slots from `slot0`; *grid_out: the workgroups launched.  inflate_release frees the idle work areas of pbs_zstd_inflate_device.
@@ -162,6 +170,11 @@ int inflate_async(const uint8_t* frames_dev, const uint64_t* foff_dev, const uin
                   const uint32_t* order_dev, size_t n, uint8_t* out_dev, uint64_t* lens_dev, uint8_t* status_dev,
                   DevArena& ar, unsigned slot0, int ncu, hipStream_t st, unsigned* grid_out = nullptr);
 void inflate_release();
+// pbs_blob_decode_inflate_device over decode_device_impl: the same internal mode
+int decode_inflate_impl(const uint8_t* blobs_dev, const uint64_t* blob_offsets, size_t n, const pbs_crypt_config* cfg,
+                        const uint8_t* expect_digests, const uint64_t* chunk_sizes, int sizes_exact, uint8_t* out_dev,
+                        size_t out_cap, uint64_t* out_offsets, uint64_t* out_lens, uint8_t* kinds, uint8_t* status,
+                        ::pbs_blob_decode_inflate_timing* timing, void* hip_stream, uint32_t* crc_out);
 }  // namespace inflate
 // pbs_crypt.hip: AES-256-GCM in place over the payloads of n blob images (plaintext at
 // blob + 44; blob i = [boff[i], boff[i+1]), offsets on host and device), IV and tag into the

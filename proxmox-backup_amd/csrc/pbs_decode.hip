@@ -263,7 +263,7 @@ __global__ void gcm_open_tag_kernel(const KeyDev* __restrict__ key, const uint8_
 }
 
 __global__ void verdict_kernel(const uint8_t* __restrict__ kind, const uint8_t* __restrict__ pre,
-                               const uint32_t* __restrict__ stored, const uint32_t* __restrict__ crc2,
+                               const uint32_t* __restrict__ stored, const uint32_t* __restrict__ crc2, int judge_crc,
                                const uint8_t* __restrict__ tag_ok, int have_cfg, const uint8_t* __restrict__ dig,
                                const uint8_t* __restrict__ expect, const uint64_t* __restrict__ ooff,
                                const uint64_t* __restrict__ expect_sizes, uint64_t n, uint8_t* __restrict__ status) {
@@ -277,7 +277,7 @@ __global__ void verdict_kernel(const uint8_t* __restrict__ kind, const uint8_t* 
         dig_ok = d == 0;
     }
     const bool size_ok = !expect_sizes || ooff[i + 1] - ooff[i] == expect_sizes[i];
-    status[i] = verdict(k, f, f || stored[i] == crc2[2 * i], have_cfg != 0, have_cfg && tag_ok[i], expect != nullptr,
+    status[i] = verdict(k, f, f || !judge_crc || stored[i] == crc2[2 * i], have_cfg != 0, have_cfg && tag_ok[i], expect != nullptr,
                         dig_ok, expect_sizes != nullptr, size_ok);
 }
 
@@ -434,6 +434,17 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
                                       const uint64_t* expect_sizes, uint8_t* out_dev, size_t out_cap,
                                       uint64_t* out_offsets, uint8_t* kinds, uint8_t* status,
                                       pbs_blob_decode_timing* timing, void* hip_stream) {
+    return pbs::decode_device_impl(blobs_dev, blob_offsets, n, cfg, expect_digests, expect_sizes, out_dev, out_cap,
+                                   out_offsets, kinds, status, timing, hip_stream, nullptr);
+}
+
+// pbs_blob_decode_device, and the internal mode of the backup session's upload (crc_out != NULL,
+// n host words): the payloads' CRCs are computed and handed out, the stored ones are not judged
+// (upload_chunk.rs:77-85), so BAD_CRC never occurs.  A blob that fails from_raw has CRC 0.
+int pbs::decode_device_impl(const uint8_t* blobs_dev, const uint64_t* blob_offsets, size_t n, const pbs_crypt_config* cfg,
+                            const uint8_t* expect_digests, const uint64_t* expect_sizes, uint8_t* out_dev, size_t out_cap,
+                            uint64_t* out_offsets, uint8_t* kinds, uint8_t* status, pbs_blob_decode_timing* timing,
+                            void* hip_stream, uint32_t* crc_out) {
     const HClock::time_point t0 = HClock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (!out_offsets) return PBS_ERR_ARG;
@@ -483,6 +494,7 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
 
     // 1. classify, output offsets
     std::vector<uint8_t> h_pre(n);
+    std::vector<uint32_t> h_crc(crc_out ? 2 * n : 0);
     if (call.rc == PBS_OK) {
         (void)hipGetLastError();
         call.ok(hipMemcpyAsync(d_boff, blob_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st)) &&
@@ -575,11 +587,15 @@ extern "C" int pbs_blob_decode_device(const uint8_t* blobs_dev, const uint64_t* 
         call.fail(digest_in_order(out_dev, out_offsets[n], d_ooff, d_digord, ndig0, digord.size(), cfg, d_dig, st));
     if (call.rc == PBS_OK) {
         hipLaunchKernelGGL(verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_kind, d_pre, d_stored,
-                           d_crc, d_tagok, cfg ? 1 : 0, d_dig, d_expect, d_ooff, d_expsize, (uint64_t)n, d_status);
+                           d_crc, crc_out ? 0 : 1, d_tagok, cfg ? 1 : 0, d_dig, d_expect, d_ooff, d_expsize, (uint64_t)n, d_status);
         hipLaunchKernelGGL(wipe_kernel, dim3((unsigned)std::min<uint64_t>(n, (uint64_t)sd.ncu * 8)), dim3(kThreads), 0, st,
                            d_kind, d_status, d_ooff, (uint64_t)n, out_dev);
         call.ok(hipGetLastError()) && call.ok(hipEventRecord(ev[4], st)) &&
-            call.ok(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st)) && call.ok(hipStreamSynchronize(st));
+            call.ok(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, st)) &&
+            (!crc_out || call.ok(hipMemcpyAsync(h_crc.data(), d_crc, 2 * n * 4, hipMemcpyDeviceToHost, st))) &&
+            call.ok(hipStreamSynchronize(st));
+        if (call.rc == PBS_OK && crc_out)
+            for (size_t i = 0; i < n; ++i) crc_out[i] = h_pre[i] ? 0 : h_crc[2 * i];
     }
     if (call.rc == PBS_OK && timing) {
         float a = 0, b = 0, c = 0, d = 0;

@@ -428,6 +428,18 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
                                               size_t out_cap, uint64_t* out_offsets, uint64_t* out_lens,
                                               uint8_t* kinds, uint8_t* status,
                                               pbs_blob_decode_inflate_timing* timing, void* hip_stream) {
+    return pbs::inflate::decode_inflate_impl(blobs_dev, blob_offsets, n, cfg, expect_digests, chunk_sizes, sizes_exact,
+                                             out_dev, out_cap, out_offsets, out_lens, kinds, status, timing, hip_stream,
+                                             nullptr);
+}
+
+// pbs_blob_decode_inflate_device; crc_out != NULL is the internal mode of decode_device_impl
+// (pbs_decode.hip), reachable from the backup session's upload alone.
+int pbs::inflate::decode_inflate_impl(const uint8_t* blobs_dev, const uint64_t* blob_offsets, size_t n,
+                                      const pbs_crypt_config* cfg, const uint8_t* expect_digests,
+                                      const uint64_t* chunk_sizes, int sizes_exact, uint8_t* out_dev, size_t out_cap,
+                                      uint64_t* out_offsets, uint64_t* out_lens, uint8_t* kinds, uint8_t* status,
+                                      pbs_blob_decode_inflate_timing* timing, void* hip_stream, uint32_t* crc_out) {
     const HClock::time_point t0 = HClock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
     if (!out_offsets) return PBS_ERR_ARG;
@@ -456,8 +468,8 @@ extern "C" int pbs_blob_decode_inflate_device(const uint8_t* blobs_dev, const ui
     std::vector<uint8_t> st1(n);
     pbs_blob_decode_timing t1;
     CallRc call;
-    if (!call.fail(pbs_blob_decode_device(blobs_dev, blob_offsets, n, cfg, nullptr, nullptr, packed, bound, poff.data(),
-                                          kinds, st1.data(), &t1, hip_stream)))
+    if (!call.fail(decode_device_impl(blobs_dev, blob_offsets, n, cfg, nullptr, nullptr, packed, bound, poff.data(), kinds,
+                                      st1.data(), &t1, hip_stream, crc_out)))
         return call.rc;
 
     // 2. copy or inflate into the slots

@@ -101,8 +101,9 @@ const uint8_t kMagics[4][8] = {{66, 171, 56, 7, 190, 131, 112, 161},
 
 // DataBlob::load_from_reader without a config: from_raw (data_blob.rs:268-290) and verify_crc.
 // kind, header length, and the first failing check (OK; an encrypted blob that passes is
-// NO_CONFIG, as pbs_blob_decode_host says it)
-uint8_t load(const uint8_t* p, size_t len, uint8_t* kind, size_t* hdr) {
+// NO_CONFIG, as pbs_blob_decode_host says it).  crc_out != NULL: the payload's CRC goes there
+// and the stored one is not judged (the backup session's upload, upload_chunk.rs:77-85)
+uint8_t load(const uint8_t* p, size_t len, uint8_t* kind, size_t* hdr, uint32_t* crc_out = nullptr) {
     *kind = PBS_BLOB_KIND_NONE;
     *hdr = 0;
     if (len < PBS_BLOB_HEADER_SIZE) return PBS_BLOB_ST_TOO_SMALL;
@@ -113,15 +114,18 @@ uint8_t load(const uint8_t* p, size_t len, uint8_t* kind, size_t* hdr) {
     if (len < h) return PBS_BLOB_ST_TOO_SMALL;
     *hdr = h;
     const uint32_t stored = (uint32_t)p[8] | (uint32_t)p[9] << 8 | (uint32_t)p[10] << 16 | (uint32_t)p[11] << 24;
-    if (stored != crc32_bytes(p + h, len - h)) return PBS_BLOB_ST_BAD_CRC;
+    const uint32_t crc = crc32_bytes(p + h, len - h);
+    if (crc_out) *crc_out = crc;
+    else if (stored != crc) return PBS_BLOB_ST_BAD_CRC;
     return *kind >= 2 ? PBS_BLOB_ST_NO_CONFIG : PBS_BLOB_ST_OK;
 }
 
 // pbs_blob_decode_inflate_device's verdict for one blob with no config, the digest `want` and a
 // slot of exactly `size` bytes (sizes_exact): load, decode_all, verify_digest, then the length
-uint8_t decode_one(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind) {
+uint8_t decode_one(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind,
+                   uint32_t* crc_out = nullptr) {
     size_t hdr = 0;
-    const uint8_t st = load(p, len, kind, &hdr);
+    const uint8_t st = load(p, len, kind, &hdr, crc_out);
     if (st != PBS_BLOB_ST_OK) return st;
     const uint8_t* pay = p + hdr;
     const size_t plen = len - hdr;
@@ -252,6 +256,17 @@ int plan(pbs_verify_host* h, const uint8_t* digests, const uint64_t* sizes, size
 
 uint8_t pbs::verify::host_blob_verdict(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind) {
     return decode_one(len ? p : kMagics[0], len, want, size, kind);
+}
+
+uint8_t pbs::verify::host_blob_verdict_upload(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size,
+                                              uint8_t* kind, uint32_t* crc) {
+    *crc = 0;
+    return decode_one(len ? p : kMagics[0], len, want, size, kind, crc);
+}
+
+uint8_t pbs::verify::host_blob_load(const uint8_t* p, size_t len, uint8_t* kind) {
+    size_t hdr = 0;
+    return load(len ? p : kMagics[0], len, kind, &hdr);
 }
 
 extern "C" int pbs_verify_begin_host(const uint8_t* store_digests, size_t m, pbs_verify_host** out, double* build_ms) {

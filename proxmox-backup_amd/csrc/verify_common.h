@@ -172,6 +172,12 @@ inline void index_entries(const uint8_t* image, const gc::IndexLayout& lo, std::
 // *kind: PBS_BLOB_KIND_*.  Throws std::bad_alloc when there is no memory for the slot.  Shared
 // with the sync job's mirror (pbs_sync_host.cpp).
 uint8_t host_blob_verdict(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind);
+// The same verdict with the stored CRC not judged and the payload's CRC in *crc (0 where from_raw
+// fails): the backup session's upload (pbs_backup_host.cpp).
+uint8_t host_blob_verdict_upload(const uint8_t* p, size_t len, const uint8_t* want, uint64_t size, uint8_t* kind,
+                                 uint32_t* crc);
+// from_raw + verify_crc alone (an encrypted blob that loads: NO_CONFIG): add_blob of the backup session
+uint8_t host_blob_load(const uint8_t* p, size_t len, uint8_t* kind);
 
 // The next batch of the whole-index call: plan items [t0, t1), t1 > t0, such that the blobs plus
 // the output slots of the unencrypted ones stay at or below `budget` (0: no bound) -- but one

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <ctime>
 #include <functional>
+#include <map>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -43,6 +44,7 @@
 #include "pbs_gc.h"
 #include "pbs_verify.h"
 #include "pbs_sync.h"
+#include "pbs_backup.h"
 
 namespace pbs {
 
@@ -1114,6 +1116,209 @@ class SyncWorker {
     bool device_;
     pbs_sync* dev_ = nullptr;
     pbs_sync_host* host_ = nullptr;
+};
+
+// One backup session on one datastore (include/pbs_backup.h: BackupEnvironment, UploadChunk and
+// ChunkStore::insert_chunk) over the store's listing: per chunk file 32 bytes of digest, its
+// length and its magic.  device == true: table, digest list and per-entry state live in the
+// memory of hip_stream's device and the blobs handed to upload are device memory; false: the
+// host mirror.  A call returns 0 or the positive PBS_BACKUP_E_* code with which the reference's
+// request fails; a negative code throws.
+class BackupSession {
+  public:
+    struct Listing {
+        std::vector<uint8_t> digests, present, kind, known;  // 32, 1, 1 and 1 per entry
+        std::vector<uint64_t> size;
+        std::vector<uint32_t> known_size;
+    };
+    struct Uploaded {
+        int code = 0;  // PBS_OK or PBS_BACKUP_E_*
+        std::vector<uint8_t> status, ins, action, is_duplicate, reg;
+        std::vector<uint32_t> crc, compressed_size;
+        uint64_t first_failed = PBS_BACKUP_NONE;
+    };
+    struct Appended {
+        int code = 0;
+        size_t n_done = 0;
+        int err = 0;
+    };
+    struct Closed {
+        int code = 0, result = 0;
+        std::vector<uint8_t> image;  // result == 0: the .didx / .fidx image
+        pbs_backup_writer_stat stat{};
+    };
+
+    BackupSession(const std::vector<uint8_t>& digests, const std::vector<uint64_t>& sizes,
+                  const std::vector<uint8_t>& kinds, size_t reserve = 0, bool device = true, void* hip_stream = nullptr)
+        : device_(device) {
+        const size_t m = sizes.size();
+        if (digests.size() != 32 * m || kinds.size() != m) throw std::invalid_argument("32 bytes of digest, a size and a kind per entry");
+        const int rc = device_ ? pbs_backup_begin(digests.data(), sizes.data(), kinds.data(), m, reserve, &dev_, &build_ms, hip_stream)
+                               : pbs_backup_begin_host(digests.data(), sizes.data(), kinds.data(), m, reserve, &host_, &build_ms);
+        check(rc, "pbs_backup_begin");
+    }
+    ~BackupSession() { close(); }
+    BackupSession(const BackupSession&) = delete;
+    BackupSession& operator=(const BackupSession&) = delete;
+
+    double build_ms = 0, ms = 0;   // of the begin; of the last register_previous / append
+    pbs_backup_timing timing{};    // of the last upload
+
+    void close() {
+        if (dev_) pbs_backup_end(dev_);
+        if (host_) pbs_backup_end_host(host_);
+        dev_ = nullptr;
+        host_ = nullptr;
+    }
+    size_t count() { return device_ ? pbs_backup_count(dev_) : pbs_backup_count_host(host_); }
+    uint32_t table_log2() { return device_ ? pbs_backup_table_log2(dev_) : pbs_backup_table_log2_host(host_); }
+    Listing listing() {
+        Listing l;
+        const size_t c = count();
+        l.digests.resize(32 * c);
+        l.present.resize(c);
+        l.kind.resize(c);
+        l.known.resize(c);
+        l.size.resize(c);
+        l.known_size.resize(c);
+        check(device_ ? pbs_backup_listing(dev_, l.digests.data(), l.present.data(), l.size.data(), l.kind.data(),
+                                           l.known.data(), l.known_size.data(), c, nullptr)
+                      : pbs_backup_listing_host(host_, l.digests.data(), l.present.data(), l.size.data(), l.kind.data(),
+                                                l.known.data(), l.known_size.data(), c, nullptr),
+              "pbs_backup_listing");
+        return l;
+    }
+    // lookup_chunk
+    std::optional<uint32_t> lookup(const uint8_t digest[32]) {
+        uint32_t size = 0;
+        const int rc = check(device_ ? pbs_backup_lookup(dev_, digest, &size) : pbs_backup_lookup_host(host_, digest, &size),
+                             "pbs_backup_lookup");
+        return rc == PBS_OK ? std::optional<uint32_t>(size) : std::nullopt;
+    }
+    pbs_backup_stat stats() {
+        pbs_backup_stat s;
+        check(device_ ? pbs_backup_stats(dev_, &s) : pbs_backup_stats_host(host_, &s), "pbs_backup_stats");
+        return s;
+    }
+    int finish() { return check(device_ ? pbs_backup_finish(dev_, nullptr) : pbs_backup_finish_host(host_, nullptr), "pbs_backup_finish"); }
+    int register_previous(const std::vector<uint8_t>& digests, const std::vector<uint32_t>& sizes) {
+        if (digests.size() != 32 * sizes.size()) throw std::invalid_argument("32 bytes of digest per size");
+        return check(device_ ? pbs_backup_register_previous(dev_, digests.data(), sizes.data(), sizes.size(), &ms)
+                             : pbs_backup_register_previous_host(host_, digests.data(), sizes.data(), sizes.size(), &ms),
+                     "pbs_backup_register_previous");
+    }
+    int register_index_image(const uint8_t* image, size_t len, size_t* n_entries = nullptr) {
+        return check(device_ ? pbs_backup_register_index_image(dev_, image, len, n_entries, &ms)
+                             : pbs_backup_register_index_image_host(host_, image, len, n_entries, &ms),
+                     "pbs_backup_register_index_image");
+    }
+    // k = blob_offsets.size() - 1 chunks for writer wid; encoded_sizes may be empty (as announced)
+    Uploaded upload(uint32_t wid, const std::vector<uint8_t>& digests, const std::vector<uint32_t>& sizes, const uint8_t* blobs,
+                    const std::vector<uint64_t>& blob_offsets, const std::vector<uint32_t>& encoded_sizes = {}) {
+        const size_t k = blob_offsets.empty() ? 0 : blob_offsets.size() - 1;
+        if (sizes.size() != k || digests.size() != 32 * k || (!encoded_sizes.empty() && encoded_sizes.size() != k))
+            throw std::invalid_argument("a digest and a size per blob");
+        Uploaded u;
+        for (auto* v : {&u.status, &u.ins, &u.action, &u.is_duplicate, &u.reg}) v->resize(k);
+        u.crc.resize(k);
+        u.compressed_size.resize(k);
+        const uint32_t* es = encoded_sizes.empty() ? nullptr : encoded_sizes.data();
+        const int rc =
+            device_ ? pbs_backup_upload(dev_, wid, digests.data(), sizes.data(), es, blobs, blob_offsets.data(), k, u.status.data(),
+                                        u.crc.data(), u.ins.data(), u.action.data(), u.is_duplicate.data(),
+                                        u.compressed_size.data(), u.reg.data(), &u.first_failed, &timing)
+                    : pbs_backup_upload_host(host_, wid, digests.data(), sizes.data(), es, blobs, blob_offsets.data(), k,
+                                             u.status.data(), u.crc.data(), u.ins.data(), u.action.data(),
+                                             u.is_duplicate.data(), u.compressed_size.data(), u.reg.data(), &u.first_failed,
+                                             &timing);
+        u.code = check(rc, "pbs_backup_upload");
+        return u;
+    }
+    // (code, wid)
+    std::pair<int, uint32_t> create_dynamic(const uint8_t* uuid = nullptr, int64_t ctime = 0) {
+        uint32_t wid = 0;
+        const int rc = check(device_ ? pbs_backup_create_dynamic(dev_, uuid, ctime, &wid)
+                                     : pbs_backup_create_dynamic_host(host_, uuid, ctime, &wid),
+                             "pbs_backup_create_dynamic");
+        if (rc == PBS_OK) entries_[wid] = 0;
+        return {rc, wid};
+    }
+    std::pair<int, uint32_t> create_fixed(uint64_t size, uint64_t chunk_size, const uint8_t* uuid = nullptr, int64_t ctime = 0,
+                                          const uint8_t* reuse_image = nullptr, size_t reuse_len = 0,
+                                          const uint8_t* reuse_csum = nullptr) {
+        uint32_t wid = 0;
+        const int rc = check(device_ ? pbs_backup_create_fixed(dev_, size, chunk_size, uuid, ctime, reuse_image, reuse_len,
+                                                               reuse_csum, &wid)
+                                     : pbs_backup_create_fixed_host(host_, size, chunk_size, uuid, ctime, reuse_image,
+                                                                    reuse_len, reuse_csum, &wid),
+                             "pbs_backup_create_fixed");
+        if (rc == PBS_OK) entries_[wid] = pbs_fidx_count(size, chunk_size);
+        return {rc, wid};
+    }
+    Appended dynamic_append(uint32_t wid, const std::vector<uint8_t>& digests, const std::vector<uint64_t>& offsets) {
+        Appended a = append(false, wid, digests, offsets);
+        if (a.code == PBS_OK) entries_[wid] += a.n_done;
+        return a;
+    }
+    Appended fixed_append(uint32_t wid, const std::vector<uint8_t>& digests, const std::vector<uint64_t>& offsets) {
+        return append(true, wid, digests, offsets);
+    }
+    Closed dynamic_close(uint32_t wid, uint64_t chunk_count, uint64_t size, const uint8_t csum[32]) {
+        return close_writer(false, wid, chunk_count, size, csum);
+    }
+    Closed fixed_close(uint32_t wid, uint64_t chunk_count, uint64_t size, const uint8_t csum[32]) {
+        return close_writer(true, wid, chunk_count, size, csum);
+    }
+    // (code, PBS_BLOB_ST_* of from_raw + verify_crc)
+    std::pair<int, uint8_t> add_blob(const uint8_t* raw, size_t len) {
+        uint8_t st = 0;
+        const int rc = check(device_ ? pbs_backup_add_blob(dev_, raw, len, &st) : pbs_backup_add_blob_host(host_, raw, len, &st),
+                             "pbs_backup_add_blob");
+        return {rc, st};
+    }
+
+  private:
+    static int check(int rc, const char* what) {
+        if (rc < 0) throw std::runtime_error(std::string(what) + ": " + pbs_strerror(rc));
+        return rc;
+    }
+    Appended append(bool fixed, uint32_t wid, const std::vector<uint8_t>& digests, const std::vector<uint64_t>& offsets) {
+        const size_t n = offsets.size();
+        if (digests.size() != 32 * n) throw std::invalid_argument("32 bytes of digest per offset");
+        Appended a;
+        int rc;
+        if (fixed)
+            rc = device_ ? pbs_backup_fixed_append(dev_, wid, digests.data(), offsets.data(), n, &a.n_done, &a.err, &ms)
+                         : pbs_backup_fixed_append_host(host_, wid, digests.data(), offsets.data(), n, &a.n_done, &a.err, &ms);
+        else
+            rc = device_ ? pbs_backup_dynamic_append(dev_, wid, digests.data(), offsets.data(), n, &a.n_done, &a.err, &ms)
+                         : pbs_backup_dynamic_append_host(host_, wid, digests.data(), offsets.data(), n, &a.n_done, &a.err, &ms);
+        a.code = check(rc, fixed ? "pbs_backup_fixed_append" : "pbs_backup_dynamic_append");
+        return a;
+    }
+    Closed close_writer(bool fixed, uint32_t wid, uint64_t chunk_count, uint64_t size, const uint8_t* csum) {
+        Closed c;
+        auto it = entries_.find(wid);
+        const size_t n = it == entries_.end() ? 0 : it->second;
+        c.image.resize(fixed ? pbs_fidx_size(n) : pbs_didx_size(n));
+        int rc;
+        if (fixed)
+            rc = device_ ? pbs_backup_fixed_close(dev_, wid, chunk_count, size, csum, c.image.data(), c.image.size(), &c.result, &c.stat)
+                         : pbs_backup_fixed_close_host(host_, wid, chunk_count, size, csum, c.image.data(), c.image.size(),
+                                                       &c.result, &c.stat);
+        else
+            rc = device_ ? pbs_backup_dynamic_close(dev_, wid, chunk_count, size, csum, c.image.data(), c.image.size(), &c.result, &c.stat)
+                         : pbs_backup_dynamic_close_host(host_, wid, chunk_count, size, csum, c.image.data(), c.image.size(),
+                                                         &c.result, &c.stat);
+        c.code = check(rc, fixed ? "pbs_backup_fixed_close" : "pbs_backup_dynamic_close");
+        if (c.code == PBS_OK && c.result != PBS_BACKUP_E_NO_WRITER) entries_.erase(wid);  // (gone, whatever the checks said)
+        if (c.code != PBS_OK || c.result != PBS_BACKUP_E_NONE) c.image.clear();
+        return c;
+    }
+    bool device_;
+    pbs_backup* dev_ = nullptr;
+    pbs_backup_host* host_ = nullptr;
+    std::map<uint32_t, size_t> entries_;  // wid -> index entries (what the close's image holds)
 };
 
 }  // namespace pbs

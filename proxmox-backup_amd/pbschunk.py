@@ -101,7 +101,14 @@ EXPORTED_SYMBOLS = (
     "pbs_sync_begin_host", "pbs_sync_count_host", "pbs_sync_table_log2_host", "pbs_sync_listing_host",
     "pbs_sync_new_group_host", "pbs_sync_end_host", "pbs_sync_plan_host", "pbs_sync_lists_host",
     "pbs_sync_submit_host", "pbs_sync_finish_host", "pbs_sync_abort_index_host", "pbs_sync_index_image_host",
-)
+    # the backup session (include/pbs_backup.h)
+    "pbs_backup_release",
+) + tuple(name + sfx for sfx in ("", "_host") for name in (
+    "pbs_backup_begin", "pbs_backup_count", "pbs_backup_table_log2", "pbs_backup_listing", "pbs_backup_lookup",
+    "pbs_backup_stats", "pbs_backup_finish", "pbs_backup_end", "pbs_backup_register_previous",
+    "pbs_backup_register_index_image", "pbs_backup_upload",
+    "pbs_backup_create_dynamic", "pbs_backup_create_fixed", "pbs_backup_dynamic_append", "pbs_backup_fixed_append",
+    "pbs_backup_dynamic_close", "pbs_backup_fixed_close", "pbs_backup_add_blob"))
 
 
 class ChunkerLibraryError(RuntimeError):
@@ -282,6 +289,36 @@ class SyncResult(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class BackupWriterStat(ctypes.Structure):
+    """pbs_backup_writer_stat: UploadStatistic and the numbers of log_upload_stat."""
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "count", "size", "compressed_size", "duplicates", "chunk_count", "archive_size", "upload_percent",
+        "client_duplicates", "server_duplicates", "duplicate_percent", "compression_percent")] + [
+        ("logged", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class BackupStat(ctypes.Structure):
+    """pbs_backup_stat: the session's counters."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("file_counter", "backup_size", "count", "size", "compressed_size",
+                                               "duplicates")] + [("open_writers", ctypes.c_uint32),
+                                                                 ("finished", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class BackupTiming(ctypes.Structure):
+    _fields_ = [("total_ms", ctypes.c_double), ("decode_ms", ctypes.c_double), ("insert_ms", ctypes.c_double),
+                ("blobs", ctypes.c_uint64), ("decoded", ctypes.c_uint64), ("encrypted", ctypes.c_uint64),
+                ("scratch_bytes", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class HybridOpts(ctypes.Structure):
@@ -487,6 +524,29 @@ def lib():
             "pbs_sync_index_image" + sfx: ([p, p, sz, ctypes.POINTER(u64), p, ctypes.POINTER(ctypes.c_uint32), psz, p, sz,
                                             p, p, sz, psz, p, sz, psz, dbl], i),
         })
+        u32, i64, pi = ctypes.c_uint32, ctypes.c_int64, ctypes.POINTER(i)
+        sig.update({
+            "pbs_backup_begin" + sfx: ([p, p, p, sz, sz, ctypes.POINTER(p), dbl] + tail, i),
+            "pbs_backup_count" + sfx: ([p], sz),
+            "pbs_backup_table_log2" + sfx: ([p], u32),
+            "pbs_backup_listing" + sfx: ([p, p, p, p, p, p, p, sz, psz], i),
+            "pbs_backup_lookup" + sfx: ([p, p, ctypes.POINTER(u32)], i),
+            "pbs_backup_stats" + sfx: ([p, ctypes.POINTER(BackupStat)], i),
+            "pbs_backup_finish" + sfx: ([p, ctypes.POINTER(BackupStat)], i),
+            "pbs_backup_end" + sfx: ([p], None),
+            "pbs_backup_register_previous" + sfx: ([p, p, p, sz, dbl], i),
+            "pbs_backup_register_index_image" + sfx: ([p, p, sz, psz, dbl], i),
+            "pbs_backup_upload" + sfx: ([p, u32, p, p, p, p, p, sz, p, p, p, p, p, p, p, ctypes.POINTER(u64),
+                                         ctypes.POINTER(BackupTiming)], i),
+            "pbs_backup_create_dynamic" + sfx: ([p, p, i64, ctypes.POINTER(u32)], i),
+            "pbs_backup_create_fixed" + sfx: ([p, u64, u64, p, i64, p, sz, p, ctypes.POINTER(u32)], i),
+            "pbs_backup_dynamic_append" + sfx: ([p, u32, p, p, sz, psz, pi, dbl], i),
+            "pbs_backup_fixed_append" + sfx: ([p, u32, p, p, sz, psz, pi, dbl], i),
+            "pbs_backup_dynamic_close" + sfx: ([p, u32, u64, u64, p, p, sz, pi, ctypes.POINTER(BackupWriterStat)], i),
+            "pbs_backup_fixed_close" + sfx: ([p, u32, u64, u64, p, p, sz, pi, ctypes.POINTER(BackupWriterStat)], i),
+            "pbs_backup_add_blob" + sfx: ([p, p, sz, p], i),
+        })
+    sig["pbs_backup_release"] = ([], None)
     for name, (args, res) in sig.items():
         if os.environ.get("PBS_LIBPBSCHUNK_AB") and not hasattr(L, name):
             continue  # (an older build in an A/B run: the symbols it has)
@@ -3135,3 +3195,289 @@ def _pull_index_files(worker, image, name, info_size, info_csum, remote_base, lo
     if not res["ok"]:
         return f"sync of {name!r} failed at fetch item {res['first_failed']}", res
     return None, res
+
+
+# ---- the backup session (include/pbs_backup.h) ----------------------------------------------------
+
+BACKUP_KIND_NOT_FILE = 254
+BACKUP_ST_BAD_PARAM, BACKUP_ST_WRONG_LENGTH = 33, 34
+(BACKUP_INS_NONE, BACKUP_INS_NEW, BACKUP_INS_DUP_SAME, BACKUP_INS_OVERWRITE_EMPTY, BACKUP_INS_DUP_KEEP_FIRST,
+ BACKUP_INS_DUP_KEEP_SMALLER, BACKUP_INS_REPLACE_BIGGER) = range(7)
+BACKUP_INS_ERR_TYPE, BACKUP_INS_ERR_READ, BACKUP_INS_ERR_UNENC_TO_ENC, BACKUP_INS_ERR_ENC_UNCOMPRESSED = 16, 17, 18, 19
+BACKUP_ACT_NONE, BACKUP_ACT_WRITE, BACKUP_ACT_TOUCH = 0, 1, 2
+BACKUP_REG_NONE, BACKUP_REG_OK, BACKUP_REG_ERR_LARGE, BACKUP_REG_ERR_MULTI_SMALL = 0, 1, 2, 3
+(BACKUP_E_FINISHED, BACKUP_E_NO_WRITER, BACKUP_E_NO_SUCH_CHUNK, BACKUP_E_STRANGE_OFFSET, BACKUP_E_INDEX_RANGE,
+ BACKUP_E_CHUNK_COUNT, BACKUP_E_SIZE, BACKUP_E_EXPECTED_COUNT, BACKUP_E_CSUM, BACKUP_E_OPEN_WRITER, BACKUP_E_NO_FILES,
+ BACKUP_E_REUSE_NO_IMAGE, BACKUP_E_REUSE_CSUM, BACKUP_E_REUSE_LENGTH, BACKUP_E_TOO_MANY_WRITERS) = range(64, 79)
+BACKUP_NONE = (1 << 64) - 1       # PBS_BACKUP_NONE: first_failed of a batch with no failing item
+
+
+def backup_release() -> None:
+    """pbs_backup_release: free the idle work areas of the backup session's calls."""
+    lib().pbs_backup_release()
+
+
+class BackupSession:
+    """One backup session on one datastore (``BackupEnvironment``, src/api2/backup/environment.rs,
+    with ``UploadChunk`` and ``ChunkStore::insert_chunk``) over the store's listing: ``listing``
+    is (digests (m, 32), file lengths (m), magics (m): BLOB_KIND_*, BLOB_KIND_NONE or
+    BACKUP_KIND_NOT_FILE).  A context manager over a pbs_backup handle (``device=True``: the
+    table, the digest list and the per-entry state live in the memory of ``hip_stream``'s device)
+    or over the host mirror's (``device=False``: no GPU).  A call returns 0 or the positive
+    BACKUP_E_* code with which the reference's request fails; a negative code raises
+    ChunkerError."""
+
+    def __init__(self, listing, reserve: int = 0, device: bool = True, hip_stream: int = 0):
+        digests = _digest_rows(listing[0])
+        m = int(digests.shape[0])
+        sizes = np.ascontiguousarray(np.asarray(listing[1], dtype=np.uint64).reshape(-1))
+        kinds = np.ascontiguousarray(np.asarray(listing[2], dtype=np.uint8).reshape(-1))
+        if sizes.size != m or kinds.size != m:
+            raise ValueError(f"{m} digests, {sizes.size} sizes, {kinds.size} kinds")
+        self.device = bool(device)
+        self._sfx = "" if self.device else "_host"
+        h, ms = ctypes.c_void_p(None), ctypes.c_double(0)
+        args = [_ptr(digests), _ptr(sizes), _ptr(kinds), m, int(reserve), ctypes.byref(h), ctypes.byref(ms)]
+        if self.device:
+            args.append(ctypes.c_void_p(hip_stream))
+        rc = self._fn("pbs_backup_begin")(*args)
+        if rc != PBS_OK:
+            raise ChunkerError(rc, "pbs_backup_begin" + self._sfx)
+        self._h = h
+        self.build_ms = float(ms.value)
+        self.ms = 0.0           # of the last register_previous / append
+        self.timing = None      # of the last upload
+        self._entries = {}      # wid -> index entries (what the close's image holds)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def close(self) -> None:
+        """pbs_backup_end.  Every later call raises ChunkerError(PBS_ERR_INVALID)."""
+        if getattr(self, "_h", None) is not None and not getattr(self, "_closed", False):
+            self._closed = True
+            self._fn("pbs_backup_end")(self._h)
+
+    def _fn(self, name: str):
+        return getattr(lib(), name + self._sfx)
+
+    def _code(self, rc: int, name: str) -> int:
+        if rc < 0:
+            raise ChunkerError(rc, name + self._sfx)
+        return int(rc)
+
+    @property
+    def count(self) -> int:
+        return int(self._fn("pbs_backup_count")(self._h))
+
+    @property
+    def table_log2(self) -> int:
+        return int(self._fn("pbs_backup_table_log2")(self._h))
+
+    def listing(self) -> dict:
+        """pbs_backup_listing: dict(digests (count, 32), present, size, kind, known, known_size)."""
+        n = ctypes.c_size_t(0)
+        self._code(self._fn("pbs_backup_listing")(self._h, None, None, None, None, None, None, 0, ctypes.byref(n)),
+                   "pbs_backup_listing")
+        c = n.value
+        out = dict(digests=np.zeros((c, 32), np.uint8), present=np.zeros(c, np.uint8), size=np.zeros(c, np.uint64),
+                   kind=np.zeros(c, np.uint8), known=np.zeros(c, np.uint8), known_size=np.zeros(c, np.uint32))
+        self._code(self._fn("pbs_backup_listing")(self._h, *[_ptr(a) for a in out.values()], c, ctypes.byref(n)),
+                   "pbs_backup_listing")
+        return out
+
+    def lookup(self, digest):
+        """lookup_chunk: the registered length, or None."""
+        d = np.frombuffer(bytes(digest), dtype=np.uint8)
+        size = ctypes.c_uint32(0)
+        rc = self._code(self._fn("pbs_backup_lookup")(self._h, _ptr(d), ctypes.byref(size)), "pbs_backup_lookup")
+        return int(size.value) if rc == 0 else None
+
+    def stats(self) -> dict:
+        s = BackupStat()
+        self._code(self._fn("pbs_backup_stats")(self._h, ctypes.byref(s)), "pbs_backup_stats")
+        return s.as_dict()
+
+    def finish(self) -> int:
+        """finish_backup's state checks: 0, BACKUP_E_OPEN_WRITER, BACKUP_E_NO_FILES or BACKUP_E_FINISHED."""
+        return self._code(self._fn("pbs_backup_finish")(self._h, None), "pbs_backup_finish")
+
+    def register_previous(self, digests, sizes) -> int:
+        """register_chunk for every chunk of the previous backup's index (mod.rs:859-863)."""
+        d = _digest_rows(digests)
+        s = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32).reshape(-1))
+        if s.size != d.shape[0]:
+            raise ValueError(f"{d.shape[0]} digests, {s.size} sizes")
+        ms = ctypes.c_double(0)
+        rc = self._fn("pbs_backup_register_previous")(self._h, _ptr(d), _ptr(s), s.size, ctypes.byref(ms))
+        self.ms = float(ms.value)
+        return self._code(rc, "pbs_backup_register_previous")
+
+    def register_index_image(self, image):
+        """register_previous from a .didx / .fidx image (bytes or a path): (code, entries).  A bad
+        image raises ChunkerError and changes nothing."""
+        if isinstance(image, (str, os.PathLike)):
+            with open(image, "rb") as f:
+                image = f.read()
+        image = bytes(image)
+        n, ms = ctypes.c_size_t(0), ctypes.c_double(0)
+        rc = self._fn("pbs_backup_register_index_image")(self._h, image, len(image), ctypes.byref(n), ctypes.byref(ms))
+        self.ms = float(ms.value)
+        return self._code(rc, "pbs_backup_register_index_image"), int(n.value)
+
+    def upload(self, wid: int, digests, sizes, blobs, blob_offsets, encoded_sizes=None):
+        """pbs_backup_upload of k chunks.  ``blobs``: for a device handle the device address of
+        the blob images, for the mirror bytes or an array; ``blob_offsets``: k + 1 offsets into
+        it.  Returns (code, dict(status, crc, ins, action, is_duplicate, compressed_size, reg,
+        first_failed))."""
+        d = _digest_rows(digests)
+        s = np.ascontiguousarray(np.asarray(sizes, dtype=np.uint32).reshape(-1))
+        off = np.ascontiguousarray(np.asarray(blob_offsets, dtype=np.uint64).reshape(-1))
+        k = max(0, off.size - 1)
+        if s.size != k or d.shape[0] != k:
+            raise ValueError(f"{k} blobs, {d.shape[0]} digests, {s.size} sizes")
+        es = None
+        if encoded_sizes is not None:
+            es = np.ascontiguousarray(np.asarray(encoded_sizes, dtype=np.uint32).reshape(-1))
+            if es.size != k:
+                raise ValueError(f"{k} blobs, {es.size} encoded sizes")
+        if self.device:
+            ptr = ctypes.c_void_p(int(blobs) or None)
+        else:
+            keep = _as_u8(blobs)
+            ptr = _ptr(keep)
+        out = dict(status=np.zeros(k, np.uint8), crc=np.zeros(k, np.uint32), ins=np.zeros(k, np.uint8),
+                   action=np.zeros(k, np.uint8), is_duplicate=np.zeros(k, np.uint8),
+                   compressed_size=np.zeros(k, np.uint32), reg=np.zeros(k, np.uint8))
+        ff, t = ctypes.c_uint64(BACKUP_NONE), BackupTiming()
+        rc = self._fn("pbs_backup_upload")(self._h, int(wid), _ptr(d), _ptr(s), None if es is None else _ptr(es), ptr,
+                                           off.ctypes.data if off.size else None, k, *[_ptr(a) for a in out.values()],
+                                           ctypes.byref(ff), ctypes.byref(t))
+        self.timing = t.as_dict()
+        out["first_failed"] = int(ff.value)
+        return self._code(rc, "pbs_backup_upload"), out
+
+    def create_dynamic(self, uuid: bytes = bytes(16), ctime: int = 0):
+        """(code, wid)."""
+        wid = ctypes.c_uint32(0)
+        rc = self._fn("pbs_backup_create_dynamic")(self._h, bytes(uuid), int(ctime), ctypes.byref(wid))
+        self._entries[int(wid.value)] = 0
+        return self._code(rc, "pbs_backup_create_dynamic"), int(wid.value)
+
+    def create_fixed(self, size: int, chunk_size: int, uuid: bytes = bytes(16), ctime: int = 0, reuse_image=None,
+                     reuse_csum=None):
+        """(code, wid).  ``reuse_csum``: the incremental writer (mod.rs:471-507) over the previous
+        index image ``reuse_image``."""
+        wid = ctypes.c_uint32(0)
+        img = None if reuse_image is None else bytes(reuse_image)
+        rc = self._fn("pbs_backup_create_fixed")(self._h, int(size), int(chunk_size), bytes(uuid), int(ctime), img,
+                                                 len(img) if img is not None else 0,
+                                                 None if reuse_csum is None else bytes(reuse_csum), ctypes.byref(wid))
+        self._entries[int(wid.value)] = -fidx_count(size, chunk_size) if chunk_size > 0 else 0  # (fixed: negative)
+        return self._code(rc, "pbs_backup_create_fixed"), int(wid.value)
+
+    def _append(self, name: str, wid: int, digests, offsets):
+        d = _digest_rows(digests)
+        o = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64).reshape(-1))
+        if o.size != d.shape[0]:
+            raise ValueError(f"{d.shape[0]} digests, {o.size} offsets")
+        done, err, ms = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_double(0)
+        rc = self._fn(name)(self._h, int(wid), _ptr(d), _ptr(o), o.size, ctypes.byref(done), ctypes.byref(err),
+                            ctypes.byref(ms))
+        self.ms = float(ms.value)
+        if self._entries.get(int(wid), -1) >= 0 and name == "pbs_backup_dynamic_append":
+            self._entries[int(wid)] += int(done.value)
+        return self._code(rc, name), int(done.value), int(err.value)
+
+    def dynamic_append(self, wid: int, digests, offsets):
+        """(code, n_done, err)."""
+        return self._append("pbs_backup_dynamic_append", wid, digests, offsets)
+
+    def fixed_append(self, wid: int, digests, offsets):
+        """(code, n_done, err)."""
+        return self._append("pbs_backup_fixed_append", wid, digests, offsets)
+
+    def _close_writer(self, name: str, wid: int, chunk_count: int, size: int, csum: bytes, image_bytes: int):
+        img = np.zeros(image_bytes, dtype=np.uint8)
+        res, st = ctypes.c_int(0), BackupWriterStat()
+        rc = self._fn(name)(self._h, int(wid), int(chunk_count), int(size), bytes(csum), _ptr(img), img.size,
+                            ctypes.byref(res), ctypes.byref(st))
+        rc = self._code(rc, name)
+        if rc == 0 and res.value != BACKUP_E_NO_WRITER:
+            self._entries.pop(int(wid), None)  # (the writer is gone, whatever the checks said)
+        ok = rc == 0 and res.value == 0
+        return rc, int(res.value), (img.tobytes() if ok else None), (st.as_dict() if ok else None)
+
+    def dynamic_close(self, wid: int, chunk_count: int, size: int, csum: bytes):
+        """(code, result, .didx image or None, stat dict or None)."""
+        return self._close_writer("pbs_backup_dynamic_close", wid, chunk_count, size, csum,
+                                  int(lib().pbs_didx_size(max(self._entries.get(int(wid), 0), 0))))
+
+    def fixed_close(self, wid: int, chunk_count: int, size: int, csum: bytes):
+        """(code, result, .fidx image or None, stat dict or None)."""
+        return self._close_writer("pbs_backup_fixed_close", wid, chunk_count, size, csum,
+                                  int(lib().pbs_fidx_size(max(-self._entries.get(int(wid), 0), 0))))
+
+    def add_blob(self, raw):
+        """(code, BLOB_ST_* of from_raw + verify_crc)."""
+        a = _as_u8(raw)
+        st = ctypes.c_uint8(0)
+        rc = self._fn("pbs_backup_add_blob")(self._h, _ptr(a), a.size, ctypes.byref(st))
+        return self._code(rc, "pbs_backup_add_blob"), int(st.value)
+
+
+def backup_snapshot(session: "BackupSession", up: dict, upload=None, previous=None, manifest_blob=None) -> dict:
+    """What ``upload_stream_host`` produced (``up``) through one session, as the client's requests
+    arrive: the previous index's chunks are registered (``previous``: (digests, sizes) or None),
+    a dynamic writer is created, the new chunks' blobs are uploaded in one batch (``upload``: for
+    a device session a function from the blob bytes (uint8 array) to (device address, keep-alive);
+    None for the mirror), every chunk is appended, the writer is closed with the client's checksum
+    and, with ``manifest_blob``, the manifest is added and the session finished.  Returns
+    dict(upload, append, close, image, stat, finish, written): ``written`` maps each digest whose
+    action is WRITE to the blob the store must hold (the CRC the session computed in bytes 8..12).
+    Stops at the first failing request; the keys after it are None."""
+    out = dict.fromkeys(("upload", "append", "close", "image", "stat", "finish"))
+    out["written"] = {}
+    if previous is not None and session.register_previous(*previous):
+        return out
+    rc, wid = session.create_dynamic()
+    if rc:
+        return out
+    ends, digests, off = up["ends"], up["digests"], up["blob_offsets"]
+    starts = np.concatenate([[0], ends[:-1]]).astype(np.uint64) if ends.size else np.zeros(0, np.uint64)
+    new = np.flatnonzero(up["known"] == 0)
+    blobs = _as_u8(up["blobs"])
+    boff = np.concatenate([[0], np.cumsum((off[1:] - off[:-1])[new])]).astype(np.uint64)
+    # (known chunks have empty blobs, so the new chunks' blobs already follow one another)
+    sizes = (ends - starts)[new].astype(np.uint32)
+    ptr, keep = upload(blobs) if session.device else (blobs, None)
+    rc, res = session.upload(wid, digests[new], sizes, ptr, boff + (off[new[0]] if new.size else 0))
+    del keep
+    out["upload"] = res
+    if rc or res["first_failed"] != BACKUP_NONE:
+        return out
+    for j, t in enumerate(new):
+        if res["action"][j] == BACKUP_ACT_WRITE:
+            b = bytearray(blobs[int(off[t]):int(off[t + 1])].tobytes())
+            b[8:12] = int(res["crc"][j]).to_bytes(4, "little")
+            out["written"][digests[t].tobytes()] = bytes(b)
+    out["append"] = session.dynamic_append(wid, digests, starts)
+    if out["append"] != (0, ends.size, 0):
+        return out
+    rc, result, image, stat = session.dynamic_close(wid, ends.size, int(ends[-1]) if ends.size else 0, up["csum"])
+    out["close"], out["image"], out["stat"] = (rc, result), image, stat
+    if rc or result or manifest_blob is None:
+        return out
+    if session.add_blob(manifest_blob) != (0, BLOB_ST_OK):
+        return out
+    out["finish"] = session.finish()
+    return out

@@ -12,12 +12,11 @@
 #include <chrono>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "gc_common.h"
+#include "live_handles.h"
 #include "pbs_backup.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
@@ -188,7 +187,7 @@ inline double ms_since(Clock::time_point t0) { return std::chrono::duration<doub
 //   int register_previous(digests, sizes, n)
 //   double last_ms       the kernels of the last register or append by HIP events, or < 0: none
 //   int verdicts(blobs, off, digests, sizes, k, pre, kinds, status, crc, tm)
-//        for the items with pre[t] == 0: kind, status (encrypted blobs that load: NO_CONFIG) and
+//        for the items with pre[t] == 0: kind, status (encrypted blobs that load: NO_CONFIG or OK) and
 //        the payload's CRC; the others keep what the arrays hold
 //   int insert_batch(digests, status, kinds, lens, sizes, k, fixed, chunk_size, small_before,
 //                    ins, action, dup, comp, reg, ms)
@@ -487,33 +486,6 @@ struct Session {
     }
 };
 
-// the handles that are alive, per handle type
-template <class H>
-struct Live {
-    std::mutex mu;
-    std::set<const H*> handles;
-    static Live& get() {
-        static Live* l = new Live;
-        return *l;
-    }
-    static bool alive(const H* h) {
-        if (!h) return false;
-        Live& l = get();
-        std::lock_guard<std::mutex> g(l.mu);
-        return l.handles.count(h) != 0;
-    }
-    static void add(const H* h) {
-        Live& l = get();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
-    static bool remove(const H* h) {
-        Live& l = get();
-        std::lock_guard<std::mutex> g(l.mu);
-        return l.handles.erase(h) != 0;
-    }
-};
-
 }  // namespace backup
 }  // namespace pbs
 
@@ -521,7 +493,7 @@ struct Live {
 // `ok` when the call may run (the device side sets the handle's device with it).  begin, end
 // and release are written out by each side.
 #define PBS_BACKUP_CALL(H, G, expr)                    \
-    if (!pbs::backup::Live<H>::alive(h)) return PBS_ERR_INVALID; \
+    if (!pbs::Live<H>::alive(h)) return PBS_ERR_INVALID; \
     G guard(h);                                        \
     if (!guard.ok) return PBS_ERR_NO_DEVICE;           \
     try {                                              \
@@ -531,8 +503,8 @@ struct Live {
     }
 
 #define PBS_BACKUP_DEFINE_ABI(SFX, H, G)                                                                                  \
-    extern "C" size_t pbs_backup_count##SFX(H* h) { return pbs::backup::Live<H>::alive(h) ? h->s.e.count() : 0; }          \
-    extern "C" uint32_t pbs_backup_table_log2##SFX(H* h) { return pbs::backup::Live<H>::alive(h) ? h->s.e.log2() : 0; }    \
+    extern "C" size_t pbs_backup_count##SFX(H* h) { return pbs::Live<H>::alive(h) ? h->s.e.count() : 0; }          \
+    extern "C" uint32_t pbs_backup_table_log2##SFX(H* h) { return pbs::Live<H>::alive(h) ? h->s.e.log2() : 0; }    \
     extern "C" int pbs_backup_listing##SFX(H* h, uint8_t* digests_out, uint8_t* present_out, uint64_t* size_out,           \
                                            uint8_t* kind_out, uint8_t* known_out, uint32_t* known_size_out, size_t cap,    \
                                            size_t* count) {                                                                \
@@ -543,7 +515,7 @@ struct Live {
         PBS_BACKUP_CALL(H, G, lookup(digest, size))                                                                        \
     }                                                                                                                      \
     extern "C" int pbs_backup_stats##SFX(H* h, pbs_backup_stat* stat) {                                                    \
-        if (!pbs::backup::Live<H>::alive(h) || !stat) return PBS_ERR_INVALID;                                              \
+        if (!pbs::Live<H>::alive(h) || !stat) return PBS_ERR_INVALID;                                              \
         h->s.stats(stat);                                                                                                  \
         return PBS_OK;                                                                                                     \
     }                                                                                                                      \

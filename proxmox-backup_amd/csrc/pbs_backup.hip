@@ -1,10 +1,10 @@
 // Device side of the backup session (include/pbs_backup.h; DESIGN.md section 10, "Backup
-// session"): the store's listing as the table of gc_table_dev.h over a digest list that grows,
+// session"): the store's listing as the growing table of grow_table_dev.h,
 // with the file's state (present, length, magic) and this session's known_chunks (known, length)
 // per entry.  Three kinds of batch run on it:
-//   register   probe or insert (sync's claim, flag, ordered append), then the highest index
+//   register   probe or insert (the claim and ordered append of grow_table_dev.h), then the highest index
 //              position of each digest writes known / known_size;
-//   upload     the blobs go through the decode-inflate path with the CRC computed and not
+//   upload     the blobs go through the blob verdict of verify_dev.h with the CRC computed and not
 //              judged; the good ones probe or insert; (entry, t) keys are sorted by entry with the
 //              stable radix sort of pbs_sort.hip and the first lane of each group walks its items
 //              in ascending t through insert_chunk's rule; a scan counts the fixed writer's
@@ -27,6 +27,7 @@
 #include "dev_arena.h"
 #include "gc_common.h"
 #include "gc_table_dev.h"
+#include "grow_table_dev.h"
 #include "pbs_backup.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
@@ -40,51 +41,13 @@ namespace backup {
 namespace {
 
 using namespace pbs::gc;
-using pbs::verify::block_count;
-using pbs::verify::verify_magic_kernel;
+using pbs::verify::blob_verdicts;
+using pbs::verify::BlobSlots;
+using pbs::verify::BlobTiming;
 
-// what the claim kernel leaves per item: the entry position found, or kRefSlot and the slot the
-// lane's digest sits in, or kRefNone for an item that takes no part
-constexpr uint64_t kRefSlot = 1ull << 63;
-constexpr uint64_t kRefNone = ~0ull;
 constexpr uint64_t kKeyNone = ~0ull;
 
-// sync_claim_kernel (pbs_sync.hip) without its first[] array; its comment states why no order
-// of the lanes changes the outcome: plain table loads may be stale across XCDs, only returned
-// atomics decide, no lane waits for another, and the table holds 2^L >= 2 (count + n) slots.
-// active (may be NULL): != PBS_BLOB_ST_OK keeps item i out.
-__global__ __launch_bounds__(kGcThreads) void bk_claim_kernel(const uint8_t* __restrict__ dig, uint64_t n,
-                                                              const uint8_t* __restrict__ active,
-                                                              const uint8_t* __restrict__ store, uint32_t count,
-                                                              uint32_t* table, uint32_t shift, uint64_t mask,
-                                                              uint64_t* __restrict__ ref) {
-    const uint64_t i = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
-    if (i >= n) return;
-    if (active && active[i] != PBS_BLOB_ST_OK) {
-        ref[i] = kRefNone;
-        return;
-    }
-    const Dig d = load_digest(dig + 32 * i);
-    const uint32_t mine = count + (uint32_t)i;
-    uint32_t j = kEmpty;
-    uint64_t s = home_slot(d.w[0], shift);
-    for (;;) {
-        uint32_t k = table[s];
-        if (k == kEmpty) {
-            if (j != kEmpty) break;  // the cluster's end, and the chunk is listed
-            k = atomicCAS(&table[s], kEmpty, mine);
-            if (k == kEmpty) break;  // the slot is this lane's, until a lower lane of its digest comes
-        }
-        if (k < count) {
-            if (k < j && same_digest(store, k, d)) j = k;
-        } else if (j == kEmpty && same_digest(dig, k - count, d)) {
-            atomicMin(&table[s], mine);
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    ref[i] = j != kEmpty ? (uint64_t)j : (kRefSlot | s);
-}
+// (grow_claim_kernel, the probe with an insert where it ends: grow_table_dev.h)
 
 // after the claim kernel has ended: who appends (the lowest lane of a new digest), and the
 // block's count of them
@@ -115,12 +78,7 @@ __global__ __launch_bounds__(kGcThreads) void bk_commit_kernel(
     __shared__ uint32_t wcnt[kGcWaves];
     const uint64_t i = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
     const bool f = i < n && fresh[i];
-    const unsigned long long b = __ballot(f);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint64_t rank = start_new[blockIdx.x] + __popcll(b & ((1ull << lane) - 1));
-    for (uint32_t w = 0; w < wave; ++w) rank += wcnt[w];
+    const uint64_t rank = ordered_rank(f, start_new[blockIdx.x], wcnt);
     if (!f) return;
     const uint32_t c = count + (uint32_t)rank;
     table[ref[i] & ~kRefSlot] = c;
@@ -234,7 +192,7 @@ __global__ __launch_bounds__(kGcThreads) void bk_register_kernel(const uint8_t* 
                             : (uint8_t)PBS_BACKUP_REG_NONE;
 }
 
-// One lane per appended digest: the probe of the verify job (the lowest entry carrying it), then
+// One lane per appended digest: the probe (lowest_entry: the lowest entry carrying it), then
 // known_chunks: len[i] = known_size or 0, kn[i] = known.  Lane n writes the scan's closing zero.
 // No kernel changes the table while this one runs, so plain loads do.
 __global__ __launch_bounds__(kGcThreads) void bk_probe_kernel(const uint8_t* __restrict__ dig, uint64_t n,
@@ -249,13 +207,7 @@ __global__ __launch_bounds__(kGcThreads) void bk_probe_kernel(const uint8_t* __r
         len[n] = 0;
         return;
     }
-    const Dig d = load_digest(dig + 32 * i);
-    uint32_t j = kEmpty;
-    for (uint64_t s = home_slot(d.w[0], shift);; s = (s + 1) & mask) {
-        const uint32_t k = table[s];
-        if (k == kEmpty) break;
-        if (k < j && same_digest(store, k, d)) j = k;
-    }
+    const uint32_t j = lowest_entry(table, store, load_digest(dig + 32 * i), shift, mask);
     const bool is_known = j != kEmpty && known[j];
     kn[i] = is_known;
     len[i] = is_known ? ksize[j] : 0;
@@ -311,154 +263,58 @@ inline uint32_t bits_for(uint64_t v) {  // the smallest b with 2^b > v
     return b;
 }
 
+constexpr GrowSlots kGrowSlots = {kBsRef, kBsCount, kBsStart, kBsScanTmp};
+constexpr BlobSlots kBlobSlots = {kBsSpans, kBsEnc, kBsOut, kBsPack};
+
 struct DevEntries {
-    int dev = 0, ncu = 0;
-    hipStream_t st = nullptr;
-    size_t n_ = 0, cap = 0;
-    uint32_t l2 = 0;
-    bool stale = false;            // a batch failed half-way: table and marks are rebuilt before the next one
+    GrowTable tab;                 // the entries' digests and the table over them
     double last_ms = 0;            // the kernels of the last register or append, by HIP events (the copies outside)
-    uint8_t* d_store = nullptr;    // 32 cap
     uint8_t* d_present = nullptr;  // cap
     uint8_t* d_kind = nullptr;     // cap
     uint8_t* d_known = nullptr;    // cap
     uint64_t* d_size = nullptr;    // cap
     uint32_t* d_ksize = nullptr;   // cap
     uint32_t* d_mark = nullptr;    // cap: zero between batches
-    uint32_t* d_table = nullptr;   // 2^l2 entry positions, kEmpty where free
 
-    size_t count() const { return n_; }
-    uint32_t log2() const { return l2; }
-
-    struct Arr {
-        void** p;
-        size_t elem;
-    };
-    void arrays(Arr (&a)[7]) {
-        a[0] = {(void**)&d_store, 32};
-        a[1] = {(void**)&d_present, 1};
-        a[2] = {(void**)&d_kind, 1};
-        a[3] = {(void**)&d_known, 1};
-        a[4] = {(void**)&d_size, 8};
-        a[5] = {(void**)&d_ksize, 4};
-        a[6] = {(void**)&d_mark, 4};
+    DevEntries() {
+        tab.side(&d_present);
+        tab.side(&d_kind);
+        tab.side(&d_known);
+        tab.side(&d_size);
+        tab.side(&d_ksize);
+        tab.side(&d_mark, 0);
     }
+    size_t count() const { return tab.count; }
+    uint32_t log2() const { return tab.log2; }
 
-    void free_all() {
-        Arr a[7];
-        arrays(a);
-        (void)hipStreamSynchronize(st);
-        for (Arr& x : a)
-            if (*x.p) (void)hipFree(*x.p);
-        if (d_table) (void)hipFree(d_table);
-    }
-
-    // the entry arrays for at least `want` entries; what they hold moves along.  Synchronous.
-    int reserve_entries(size_t want) {
-        if (want <= cap) return PBS_OK;
-        const size_t ncap = std::max(want, cap + cap / 2);
-        Arr a[7];
-        arrays(a);
-        void* fresh[7] = {};
-        CallRc rc;
-        for (int i = 0; i < 7 && rc.rc == PBS_OK; ++i)
-            if (hipMalloc(&fresh[i], a[i].elem * ncap) != hipSuccess) {
-                (void)hipGetLastError();
-                rc.fail(PBS_ERR_NOMEM);
-            }
-        for (int i = 0; i < 6 && rc.rc == PBS_OK && n_; ++i)
-            rc.ok(hipMemcpyAsync(fresh[i], *a[i].p, a[i].elem * n_, hipMemcpyDeviceToDevice, st));
-        if (rc.rc == PBS_OK) rc.ok(hipMemsetAsync(fresh[6], 0, 4 * ncap, st));
-        if (hipStreamSynchronize(st) != hipSuccess) rc.fail(PBS_ERR_HIP);
-        for (int i = 0; i < 7; ++i) {
-            if (rc.rc == PBS_OK) std::swap(*a[i].p, fresh[i]);
-            if (fresh[i]) (void)hipFree(fresh[i]);
-        }
-        if (rc.rc == PBS_OK) cap = ncap;
-        return rc.rc;
-    }
-
-    // the table at 2^log2 slots over all entries (gc_build_kernel), queued on the stream
-    int rebuild_table(uint32_t log2v) {
-        const size_t slots = (size_t)1 << log2v;
-        if (log2v != l2 || !d_table) {
-            uint32_t* t = nullptr;
-            if (log2v >= 8 * sizeof(size_t) - 3 || hipMalloc(&t, slots * 4) != hipSuccess) {
-                (void)hipGetLastError();
-                return PBS_ERR_NOMEM;
-            }
-            if (d_table) {
-                (void)hipStreamSynchronize(st);
-                (void)hipFree(d_table);
-            }
-            d_table = t;
-            l2 = log2v;
-        }
-        CallRc rc;
-        (void)hipGetLastError();
-        if (rc.ok(hipMemsetAsync(d_table, 0xFF, slots * 4, st)) && n_) {
-            hipLaunchKernelGGL(gc_build_kernel, dim3(blocks_for(n_)), dim3(kGcThreads), 0, st, d_store, (uint64_t)n_,
-                               d_table, 64 - log2v, (uint64_t)slots - 1);
-            rc.ok(hipGetLastError());
-        }
-        return rc.rc;
-    }
-
-    // Room for n more entries and the table's growth before a batch of n items (sync's rule),
-    // then claim, flag, ordered append and the items' entry positions into pos (device, n).
-    // d_dig: the batch's digests (device); active: NULL or the items' status (device).
+    // A batch of n items against the list (GrowTable::append with one list: the digests that
+    // are appended), then the items' entry positions into pos (device, n).  d_dig: the batch's
+    // digests (device); active: NULL or the items' status (device).
     int resolve(DevArena& ar, const uint8_t* d_dig, const uint8_t* active, size_t n, uint32_t* pos) {
-        int r = reserve_entries(n_ + n);
-        if (r != PBS_OK) return r;
         const unsigned nb = blocks_for(n);
-        uint64_t* ref = ar.get<uint64_t>(kBsRef, 8 * n);
         uint8_t* fresh = ar.get<uint8_t>(kBsFresh, n);
-        unsigned long long* counts = ar.get<unsigned long long>(kBsCount, ((size_t)nb + 1) * 8);
-        unsigned long long* starts = ar.get<unsigned long long>(kBsStart, ((size_t)nb + 1) * 8);
-        size_t tb = 0;
-        (void)exclusive_sum_u64(nullptr, &tb, nullptr, nullptr, nb + 1, st);
-        void* tmp = ar.get<void>(kBsScanTmp, tb);
-        if (!ref || !fresh || !counts || !starts || !tmp) return PBS_ERR_NOMEM;
-        CallRc rc;
-        (void)hipGetLastError();
-        const uint32_t want = sync::plan_log2(n_, n, l2);
-        if (want != l2 || stale) {
-            rc.fail(rebuild_table(want));
-            if (rc.rc == PBS_OK && stale) rc.ok(hipMemsetAsync(d_mark, 0, 4 * cap, st));
-        }
-        if (rc.rc != PBS_OK) return rc.rc;
-        stale = true;  // (until the commit has been seen to end)
-        const uint32_t count = (uint32_t)n_, shift = 64 - l2;
-        const uint64_t mask = (1ull << l2) - 1;
+        if (!fresh) return PBS_ERR_NOMEM;
+        hipStream_t st = tab.st;
         unsigned long long total = 0;
-        rc.ok(hipMemsetAsync(counts + nb, 0, 8, st));  // (the exclusive sum's last value is then the total)
-        if (rc.rc == PBS_OK) {
-            hipLaunchKernelGGL(bk_claim_kernel, dim3(nb), dim3(kGcThreads), 0, st, d_dig, (uint64_t)n, active, d_store, count,
-                               d_table, shift, mask, ref);
-            hipLaunchKernelGGL(bk_flag_kernel, dim3(nb), dim3(kGcThreads), 0, st, ref, (uint64_t)n, count, d_table, fresh,
-                               counts);
-            rc.ok(hipGetLastError());
-        }
-        if (rc.rc == PBS_OK)
-            rc.ok(exclusive_sum_u64(tmp, &tb, reinterpret_cast<const uint64_t*>(counts), reinterpret_cast<uint64_t*>(starts),
-                                    nb + 1, st));
-        if (rc.rc == PBS_OK) {
-            hipLaunchKernelGGL(bk_commit_kernel, dim3(nb), dim3(kGcThreads), 0, st, d_dig, ref, fresh, (uint64_t)n, count,
-                               starts, d_table, d_store, d_present, d_size, d_kind, d_known, d_ksize);
-            hipLaunchKernelGGL(bk_pos_kernel, dim3(nb), dim3(kGcThreads), 0, st, ref, (uint64_t)n, d_table, pos);
-            rc.ok(hipGetLastError()) && rc.ok(hipMemcpyAsync(&total, starts + nb, 8, hipMemcpyDeviceToHost, st));
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) rc.fail(PBS_ERR_HIP);
-        if (rc.rc == PBS_OK && total > n) rc.fail(PBS_ERR_HIP);  // (never: one flag per lane)
-        if (rc.rc != PBS_OK) return rc.rc;
-        stale = false;
-        n_ += (size_t)total;
-        return PBS_OK;
+        return tab.append(
+            ar, kGrowSlots, d_dig, active, nullptr, n, 1, &total,
+            [&](const uint64_t* ref, uint32_t count, unsigned long long* const* counts) {
+                hipLaunchKernelGGL(bk_flag_kernel, dim3(nb), dim3(kGcThreads), 0, st, ref, (uint64_t)n, count, tab.d_table,
+                                   fresh, counts[0]);
+                return hipGetLastError();
+            },
+            [&](const uint64_t* ref, uint32_t count, unsigned long long* const* starts) {
+                hipLaunchKernelGGL(bk_commit_kernel, dim3(nb), dim3(kGcThreads), 0, st, d_dig, ref, fresh, (uint64_t)n, count,
+                                   starts[0], tab.d_table, tab.d_store, d_present, d_size, d_kind, d_known, d_ksize);
+                hipLaunchKernelGGL(bk_pos_kernel, dim3(nb), dim3(kGcThreads), 0, st, ref, (uint64_t)n, tab.d_table, pos);
+                return hipGetLastError();
+            });
     }
 
     int listing(uint8_t* d, uint8_t* p, uint64_t* s, uint8_t* k, uint8_t* kn, uint32_t* ks, size_t n) {
+        hipStream_t st = tab.st;
         CallRc rc;
-        if (d) rc.ok(hipMemcpyAsync(d, d_store, 32 * n, hipMemcpyDeviceToHost, st));
+        if (d) rc.ok(hipMemcpyAsync(d, tab.d_store, 32 * n, hipMemcpyDeviceToHost, st));
         if (p && rc.rc == PBS_OK) rc.ok(hipMemcpyAsync(p, d_present, n, hipMemcpyDeviceToHost, st));
         if (s && rc.rc == PBS_OK) rc.ok(hipMemcpyAsync(s, d_size, 8 * n, hipMemcpyDeviceToHost, st));
         if (k && rc.rc == PBS_OK) rc.ok(hipMemcpyAsync(k, d_kind, n, hipMemcpyDeviceToHost, st));
@@ -477,28 +333,29 @@ struct DevEntries {
     // the probe of n digests (host): len (n + 1) and kn (n) stay in the arena; `after_copy` (may
     // be NULL) is recorded between the upload and the kernel
     int probe(DevArena& ar, const uint8_t* digests, size_t n, uint64_t** len, uint8_t** kn, hipEvent_t after_copy = nullptr) {
+        hipStream_t st = tab.st;
         uint8_t* d_dig = ar.get<uint8_t>(kBsDig, 32 * n);
         *len = ar.get<uint64_t>(kBsLens, 8 * (n + 1));
         *kn = ar.get<uint8_t>(kBsKn, n);
         if (!d_dig || !*len || !*kn) return PBS_ERR_NOMEM;
         CallRc rc;
         (void)hipGetLastError();
-        if (stale) {  // (a batch failed half-way: the table holds provisional values)
-            rc.fail(rebuild_table(l2)) && rc.ok(hipMemsetAsync(d_mark, 0, 4 * cap, st));
-            if (rc.rc != PBS_OK) return rc.rc;
-            stale = false;
+        if (tab.stale) {  // (a batch failed half-way: the table holds provisional values)
+            if (!rc.fail(tab.rebuild_stale(tab.log2))) return rc.rc;
+            tab.stale = false;
         }
         if (rc.ok(hipMemcpyAsync(d_dig, digests, 32 * n, hipMemcpyHostToDevice, st)) &&
             (!after_copy || rc.ok(hipEventRecord(after_copy, st)))) {
-            hipLaunchKernelGGL(bk_probe_kernel, dim3(blocks_for(n + 1)), dim3(kGcThreads), 0, st, d_dig, (uint64_t)n, d_store,
-                               d_table, 64 - l2, (1ull << l2) - 1, d_known, d_ksize, *len, *kn);
+            hipLaunchKernelGGL(bk_probe_kernel, dim3(blocks_for(n + 1)), dim3(kGcThreads), 0, st, d_dig, (uint64_t)n, tab.d_store,
+                               tab.d_table, 64 - tab.log2, (1ull << tab.log2) - 1, d_known, d_ksize, *len, *kn);
             rc.ok(hipGetLastError());
         }
         return rc.rc;
     }
 
     int lookup(const uint8_t* digest, bool* is_known, uint32_t* sz) {
-        ArenaLease ar(bpool(), dev);
+        hipStream_t st = tab.st;
+        ArenaLease ar(bpool(), tab.dev);
         uint64_t* len = nullptr;
         uint8_t* kn = nullptr;
         CallRc rc;
@@ -513,7 +370,8 @@ struct DevEntries {
     }
 
     int register_previous(const uint8_t* digests, const uint32_t* sizes, size_t n) {
-        ArenaLease ar(bpool(), dev);
+        hipStream_t st = tab.st;
+        ArenaLease ar(bpool(), tab.dev);
         uint8_t* d_dig = ar->get<uint8_t>(kBsDig, 32 * n);
         uint32_t* d_sizes = ar->get<uint32_t>(kBsSizes, 4 * n);
         uint32_t* pos = ar->get<uint32_t>(kBsPos, 4 * n);
@@ -538,80 +396,29 @@ struct DevEntries {
         return rc.rc;
     }
 
-    // The blobs with pre[t] == 0 through the decode-inflate path with no config, the announced
-    // digests and sizes, sizes_exact = 1 and the CRC handed out instead of judged.  As the verify
-    // job does it: the magic of every blob is read first and an encrypted blob gets a zero-length
-    // slot; the decoder takes blobs that follow one another, so a run between two refused items
-    // goes per call.
+    // the blob verdict of verify_dev.h with the CRC handed out instead of judged
     int verdicts(const uint8_t* blobs_dev, const uint64_t* off, const uint8_t* digests, const uint32_t* sizes, size_t k,
                  const uint8_t* pre, uint8_t* kinds, uint8_t* status, uint32_t* crc, pbs_backup_timing* tm) {
-        ArenaLease ar(bpool(), dev);
-        if (!blobs_dev) {  // (k empty blobs: the kernels still want an address)
-            blobs_dev = ar->get<uint8_t>(kBsPack, 1);
-            if (!blobs_dev) return PBS_ERR_NOMEM;
-        }
-        std::vector<uint64_t> spans(2 * k);
-        for (size_t t = 0; t < k; ++t) {
-            spans[2 * t] = off[t];
-            spans[2 * t + 1] = pre[t] ? 0 : off[t + 1] - off[t];
-        }
-        std::vector<uint8_t> enc(k, 0);
-        uint64_t* d_spans = ar->get<uint64_t>(kBsSpans, 16 * k);
-        uint8_t* d_enc = ar->get<uint8_t>(kBsEnc, k);
-        if (!d_spans || !d_enc) return PBS_ERR_NOMEM;
-        CallRc call;
-        (void)hipGetLastError();
-        if (call.ok(hipMemcpyAsync(d_spans, spans.data(), 16 * k, hipMemcpyHostToDevice, st))) {
-            hipLaunchKernelGGL(verify_magic_kernel, dim3(blocks_for(k)), dim3(kGcThreads), 0, st, blobs_dev, d_spans,
-                               (uint64_t)k, d_enc);
-            call.ok(hipGetLastError()) && call.ok(hipMemcpyAsync(enc.data(), d_enc, k, hipMemcpyDeviceToHost, st));
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) call.fail(PBS_ERR_HIP);
-        if (call.rc != PBS_OK) return call.rc;
-        std::vector<uint64_t> csz, ooff, olens;
-        for (size_t a = 0; a < k;) {
-            if (pre[a]) {
-                ++a;
-                continue;
-            }
-            size_t b = a;
-            while (b < k && !pre[b]) ++b;
-            const size_t cnt = b - a;
-            csz.assign(cnt, 0);
-            uint64_t total = 0;
-            bool plain = false;
-            for (size_t t = a; t < b; ++t) {
-                tm->encrypted += enc[t];
-                if (enc[t]) continue;
-                plain = true;
-                csz[t - a] = sizes[t];  // (<= 16 MiB each: the schema check came first)
-                total += csz[t - a];
-            }
-            if (total > SIZE_MAX) return PBS_ERR_NOMEM;
-            uint8_t* d_out = plain ? ar->get<uint8_t>(kBsOut, (size_t)total, false) : nullptr;
-            if (plain && !d_out) return PBS_ERR_NOMEM;
-            ooff.assign(cnt + 1, 0);
-            olens.assign(cnt, 0);
-            pbs_blob_decode_inflate_timing dt;
-            const int rc = pbs::inflate::decode_inflate_impl(blobs_dev, off + a, cnt, nullptr, digests + 32 * a, csz.data(), 1,
-                                                             d_out, (size_t)total, ooff.data(), olens.data(), kinds + a,
-                                                             status + a, &dt, st, crc + a);
-            if (rc != PBS_OK) return rc;
-            tm->decode_ms += dt.base.total_ms;
-            tm->decoded += cnt;
-            tm->scratch_bytes += total;
-            a = b;
-        }
-        return PBS_OK;
+        ArenaLease ar(bpool(), tab.dev);
+        BlobTiming bt;
+        // (sizes: <= 16 MiB each, the schema check came first)
+        const int rc = blob_verdicts(*ar, kBlobSlots, tab.st, blobs_dev, off, pre, digests,
+                                     [&](size_t t) -> uint64_t { return sizes[t]; }, k, kinds, status, crc, &bt);
+        tm->decode_ms += bt.decode_ms;
+        tm->decoded += bt.decoded;
+        tm->encrypted += bt.encrypted;
+        tm->scratch_bytes += bt.scratch_bytes;
+        return rc;
     }
 
     int insert_batch(const uint8_t* digests, const uint8_t* status, const uint8_t* kinds, const uint32_t* lens,
                      const uint32_t* sizes, size_t k, bool fixed, uint64_t chunk_size, uint64_t small_before, uint8_t* ins,
                      uint8_t* action, uint8_t* dup, uint32_t* comp, uint8_t* reg, double* ms) {
-        ArenaLease ar(bpool(), dev);
+        hipStream_t st = tab.st;
+        ArenaLease ar(bpool(), tab.dev);
         const unsigned nb = blocks_for(k), nb1 = blocks_for(k + 1);
         // the key's layout: t in the low tb bits, the entry above; the refused items' key is all ones
-        const uint32_t tb = std::max<uint32_t>(1, bits_for(k - 1)), pb = bits_for((uint64_t)n_ + k);
+        const uint32_t tb = std::max<uint32_t>(1, bits_for(k - 1)), pb = bits_for((uint64_t)tab.count + k);
         size_t sort_b = 0, scan_b = 0;
         (void)radix_sort(nullptr, &sort_b, nullptr, nullptr, nullptr, nullptr, k, (int)tb, (int)(tb + pb), st);
         (void)exclusive_sum_u64(nullptr, &scan_b, nullptr, nullptr, (uint32_t)(k + 1), st);
@@ -684,6 +491,7 @@ struct DevEntries {
     // after a check kernel: the lowest failing i, its code, and the first n_done values of out64
     int collect(const unsigned long long* first, const int* code, const uint64_t* d_out64, size_t n, size_t* n_done, int* err,
                 uint64_t* out64) {
+        hipStream_t st = tab.st;
         unsigned long long f = 0;
         CallRc rc;
         rc.ok(hipMemcpyAsync(&f, first, 8, hipMemcpyDeviceToHost, st)) && rc.ok(hipStreamSynchronize(st));
@@ -699,7 +507,8 @@ struct DevEntries {
 
     int append_common(bool fixed, const uint8_t* digests, const uint64_t* offsets, size_t n, uint64_t start, uint64_t size,
                       uint64_t chunk_size, uint64_t index_length, size_t* n_done, int* err, uint64_t* out64) {
-        ArenaLease ar(bpool(), dev);
+        hipStream_t st = tab.st;
+        ArenaLease ar(bpool(), tab.dev);
         uint64_t* len = nullptr;
         uint8_t* kn = nullptr;
         uint64_t* d_off = ar->get<uint64_t>(kBsOffsets, 8 * n);
@@ -755,11 +564,11 @@ namespace {
 struct HandleGuard {
     pbs::DeviceGuard dg;
     bool ok;
-    explicit HandleGuard(const pbs_backup* h) : dg(h->s.e.dev), ok(dg.ok) {}
+    explicit HandleGuard(const pbs_backup* h) : dg(h->s.e.tab.dev), ok(dg.ok) {}
 };
 void free_handle(pbs_backup* h) {
-    pbs::DeviceGuard dg(h->s.e.dev);
-    if (dg.ok) h->s.e.free_all();
+    pbs::DeviceGuard dg(h->s.e.tab.dev);
+    if (dg.ok) h->s.e.tab.free_all();
     delete h;
 }
 }  // namespace
@@ -782,33 +591,15 @@ extern "C" int pbs_backup_begin(const uint8_t* store_digests, const uint64_t* st
     pbs_backup* h = new (std::nothrow) pbs_backup;
     if (!h) return PBS_ERR_NOMEM;
     DevEntries& e = h->s.e;
-    e.dev = sd.dev;
-    e.ncu = sd.ncu;
-    e.st = st;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    CallRc rc;
-    rc.fail(e.reserve_entries(std::max<size_t>(m + reserve, 1)));
-    if (rc.rc == PBS_OK && m) {
-        rc.ok(hipMemcpyAsync(e.d_store, store_digests, 32 * m, hipMemcpyHostToDevice, st)) &&
-            rc.ok(hipMemcpyAsync(e.d_size, store_sizes, 8 * m, hipMemcpyHostToDevice, st)) &&
-            rc.ok(hipMemcpyAsync(e.d_kind, store_kinds, m, hipMemcpyHostToDevice, st)) &&
-            rc.ok(hipMemsetAsync(e.d_present, 1, m, st)) && rc.ok(hipMemsetAsync(e.d_known, 0, m, st)) &&
-            rc.ok(hipMemsetAsync(e.d_ksize, 0, 4 * m, st));
-    }
-    e.n_ = m;
-    if (rc.rc == PBS_OK && rc.ok(hipEventCreate(&e0)) && rc.ok(hipEventCreate(&e1)) && rc.ok(hipEventRecord(e0, st)))
-        rc.fail(e.rebuild_table(sync::begin_log2(m, reserve)));
-    if (rc.rc == PBS_OK && rc.ok(hipEventRecord(e1, st))) rc.ok(hipStreamSynchronize(st));
-    if (rc.rc == PBS_OK && build_ms) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *build_ms = ms;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc.rc != PBS_OK) {
+    const int rc = e.tab.begin(sd, st, store_digests, m, reserve, build_ms, [&](CallRc& up) {
+        up.ok(hipMemcpyAsync(e.d_size, store_sizes, 8 * m, hipMemcpyHostToDevice, st)) &&
+            up.ok(hipMemcpyAsync(e.d_kind, store_kinds, m, hipMemcpyHostToDevice, st)) &&
+            up.ok(hipMemsetAsync(e.d_present, 1, m, st)) && up.ok(hipMemsetAsync(e.d_known, 0, m, st)) &&
+            up.ok(hipMemsetAsync(e.d_ksize, 0, 4 * m, st));
+    });
+    if (rc != PBS_OK) {
         free_handle(h);
-        return rc.rc;
+        return rc;
     }
     Live<pbs_backup>::add(h);
     *out = h;

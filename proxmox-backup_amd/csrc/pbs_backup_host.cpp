@@ -200,14 +200,14 @@ extern "C" int pbs_backup_begin_host(const uint8_t* store_digests, const uint64_
         delete h;
         return PBS_ERR_NOMEM;
     }
-    Live<pbs_backup_host>::add(h);
+    pbs::Live<pbs_backup_host>::add(h);
     *out = h;
     if (build_ms) *build_ms = ms_since(t0);
     return PBS_OK;
 }
 
 extern "C" void pbs_backup_end_host(pbs_backup_host* h) {
-    if (h && Live<pbs_backup_host>::remove(h)) delete h;
+    if (h && pbs::Live<pbs_backup_host>::remove(h)) delete h;
 }
 
 PBS_BACKUP_DEFINE_ABI(_host, pbs_backup_host, NoGuard)

@@ -11,14 +11,13 @@
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "dev_arena.h"
 #include "gc_common.h"
 #include "gc_table_dev.h"
+#include "live_handles.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
 #include "pbs_gc.h"
@@ -70,33 +69,11 @@ __global__ __launch_bounds__(kGcThreads) void gc_mark_kernel(const uint8_t* __re
         missing = !chunk;
         miss[i] = missing ? 1 : 0;
     }
-    const unsigned long long b = __ballot(missing);
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t c = 0;
-        for (int w = 0; w < kGcWaves; ++w) c += wcnt[w];
-        block_missing[blockIdx.x] = c;
-    }
+    const uint32_t c = block_count(missing, wcnt);
+    if (threadIdx.x == 0) block_missing[blockIdx.x] = c;
 }
 
-// The positions of the missing entries, ascending: block_start[b] is the exclusive sum of the
-// blocks' counts, a lane's rank inside its block comes from the ballots.
-__global__ __launch_bounds__(kGcThreads) void gc_compact_kernel(const uint8_t* __restrict__ miss, uint64_t n,
-                                                                const unsigned long long* __restrict__ block_start,
-                                                                uint32_t* __restrict__ out, uint64_t cap) {
-    __shared__ uint32_t wcnt[kGcWaves];
-    const uint64_t i = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
-    const bool missing = i < n && miss[i] != 0;
-    const unsigned long long b = __ballot(missing);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (!missing) return;
-    uint64_t rank = block_start[blockIdx.x] + __popcll(b & ((1ull << lane) - 1));
-    for (uint32_t w = 0; w < wave; ++w) rank += wcnt[w];
-    if (rank < cap) out[rank] = (uint32_t)i;
-}
+// (gc_compact_kernel, the positions of the missing entries in ascending order: gc_table_dev.h)
 
 // One lane per store entry: what phase 1 would have touched.  A referenced .bad entry probes the
 // table for a flags == 0 entry with its digest; they are rare.
@@ -191,20 +168,7 @@ ArenaPool& gpool() {
 
 enum GSlot : unsigned { kGsMiss, kGsCount, kGsStart, kGsScanTmp, kGsOut, kGsImage, kGsSizes, kGsAtimes, kGsTouched, kGsActions, kGsCtr };
 
-struct Live {
-    std::mutex mu;
-    std::set<const pbs_gc*> handles;
-};
-Live& live() {
-    static Live* l = new Live;
-    return *l;
-}
-bool alive(const pbs_gc* h) {
-    if (!h) return false;
-    Live& l = live();
-    std::lock_guard<std::mutex> g(l.mu);
-    return l.handles.count(h) != 0;
-}
+using Handles = Live<pbs_gc>;
 
 void free_handle(pbs_gc* h) {
     DeviceGuard dg(h->dev);
@@ -256,8 +220,8 @@ int mark_on(pbs_gc* h, DevArena& ar, const uint8_t* base_dev, size_t stride, siz
     if (rc.rc == PBS_OK && rc.ok(exclusive_sum_u64(tmp, &tb, reinterpret_cast<const uint64_t*>(count),
                                                    reinterpret_cast<uint64_t*>(start), nb + 1, st)) &&
         ncap) {
-        hipLaunchKernelGGL(gc_compact_kernel, dim3(nb), dim3(kGcThreads), 0, st, miss, (uint64_t)n, start, out,
-                           (uint64_t)ncap);
+        hipLaunchKernelGGL(gc_compact_kernel<false>, dim3(nb), dim3(kGcThreads), 0, st, miss, (uint64_t)n, start, out,
+                           (uint64_t)ncap, (const uint32_t*)nullptr, (uint32_t*)nullptr);
         rc.ok(hipGetLastError());
     }
     if (rc.rc == PBS_OK && rc.ok(hipEventRecord(e1, st)) &&
@@ -285,7 +249,7 @@ int mark_call(pbs_gc* h, const uint8_t* base_dev, size_t stride, size_t n, bool 
               uint32_t* missing_pos, size_t cap, size_t* n_missing, double* mark_ms) {
     if (n_missing) *n_missing = 0;
     if (mark_ms) *mark_ms = 0;
-    if (!alive(h) || !mark_args_valid(base_dev, stride, n, missing_pos, cap)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !mark_args_valid(base_dev, stride, n, missing_pos, cap)) return PBS_ERR_INVALID;
     DeviceGuard dg(h->dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
     ArenaLease ar(gpool(), h->dev);
@@ -356,16 +320,12 @@ extern "C" int pbs_gc_begin(const uint8_t* store_digests, const uint8_t* flags, 
         free_handle(h);
         return rc.rc;
     }
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
+    Handles::add(h);
     *out = h;
     return PBS_OK;
 }
 
-extern "C" uint32_t pbs_gc_table_log2(const pbs_gc* h) { return alive(h) ? h->log2 : 0; }
+extern "C" uint32_t pbs_gc_table_log2(const pbs_gc* h) { return Handles::alive(h) ? h->log2 : 0; }
 
 extern "C" int pbs_gc_mark_device(pbs_gc* h, const uint8_t* base_dev, size_t stride, size_t n, uint64_t index_bytes,
                                   uint32_t* missing_pos, size_t cap, size_t* n_missing, double* mark_ms) {
@@ -381,7 +341,7 @@ extern "C" int pbs_gc_mark_index_image(pbs_gc* h, const uint8_t* image, size_t l
                                        size_t* n_missing, double* mark_ms) {
     if (n_missing) *n_missing = 0;
     if (mark_ms) *mark_ms = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     IndexLayout lo;
     int rc = index_layout(image, len, &lo);
     if (rc != PBS_OK) return rc;
@@ -410,7 +370,7 @@ extern "C" int pbs_gc_mark_index_image(pbs_gc* h, const uint8_t* image, size_t l
 
 extern "C" int pbs_gc_touched(pbs_gc* h, uint8_t* touched, size_t* n_touched) {
     if (n_touched) *n_touched = 0;
-    if (!alive(h) || (h->m && !touched)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || (h->m && !touched)) return PBS_ERR_INVALID;
     if (h->m == 0) return PBS_OK;
     DeviceGuard dg(h->dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
@@ -432,7 +392,7 @@ extern "C" int pbs_gc_touched(pbs_gc* h, uint8_t* touched, size_t* n_touched) {
 extern "C" int pbs_gc_sweep(pbs_gc* h, const uint64_t* sizes, const int64_t* atimes, int64_t phase1_start,
                             int64_t oldest_writer, uint8_t* actions, pbs_gc_status* status, double* sweep_ms) {
     if (sweep_ms) *sweep_ms = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     const size_t m = h->m;
     int64_t min_atime = 0;
     if ((m && (!sizes || !atimes)) || !sweep_min_atime(phase1_start, oldest_writer, &min_atime)) return PBS_ERR_INVALID;
@@ -488,11 +448,5 @@ extern "C" int pbs_gc_sweep(pbs_gc* h, const uint64_t* sizes, const int64_t* ati
 }
 
 extern "C" void pbs_gc_end(pbs_gc* h) {
-    if (!h) return;
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        if (!l.handles.erase(h)) return;
-    }
-    free_handle(h);
+    if (h && Handles::remove(h)) free_handle(h);
 }

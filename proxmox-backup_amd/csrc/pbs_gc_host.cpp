@@ -7,12 +7,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "gc_common.h"
+#include "live_handles.h"
 #include "pbs_chunker.h"
 #include "pbs_gc.h"
 
@@ -42,20 +41,7 @@ inline uint64_t be64(const uint8_t* p) {
     return v;
 }
 
-struct Live {
-    std::mutex mu;
-    std::set<pbs_gc_host*> handles;
-};
-Live& live() {
-    static Live* l = new Live;
-    return *l;
-}
-bool alive(pbs_gc_host* h) {
-    if (!h) return false;
-    Live& l = live();
-    std::lock_guard<std::mutex> g(l.mu);
-    return l.handles.count(h) != 0;
-}
+using Handles = pbs::Live<pbs_gc_host>;
 
 // calls f(j) for every store entry j that carries the digest `d`
 template <class F>
@@ -72,7 +58,7 @@ int mark(pbs_gc_host* h, const uint8_t* base, size_t stride, size_t n, bool whol
     const Clock::time_point t0 = Clock::now();
     if (n_missing) *n_missing = 0;
     if (mark_ms) *mark_ms = 0;
-    if (!alive(h) || !mark_args_valid(base, stride, n, missing_pos, cap)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !mark_args_valid(base, stride, n, missing_pos, cap)) return PBS_ERR_INVALID;
     size_t missing = 0;
     for (size_t i = 0; i < n; ++i) {
         bool chunk = false;
@@ -136,11 +122,7 @@ extern "C" int pbs_gc_begin_host(const uint8_t* store_digests, const uint8_t* fl
         delete h;
         return PBS_ERR_NOMEM;
     }
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
+    Handles::add(h);
     *out = h;
     if (build_ms) *build_ms = ms_since(t0);
     return PBS_OK;
@@ -160,7 +142,7 @@ extern "C" int pbs_gc_mark_index_image_host(pbs_gc_host* h, const uint8_t* image
                                             size_t cap, size_t* n_missing, double* mark_ms) {
     if (n_missing) *n_missing = 0;
     if (mark_ms) *mark_ms = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     IndexLayout lo;
     const int rc = index_layout(image, len, &lo);
     if (rc != PBS_OK) return rc;
@@ -169,7 +151,7 @@ extern "C" int pbs_gc_mark_index_image_host(pbs_gc_host* h, const uint8_t* image
 
 extern "C" int pbs_gc_touched_host(pbs_gc_host* h, uint8_t* touched, size_t* n_touched) {
     if (n_touched) *n_touched = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     const size_t m = h->flags.size();
     if (m && !touched) return PBS_ERR_INVALID;
     size_t cnt = 0;
@@ -182,7 +164,7 @@ extern "C" int pbs_gc_sweep_host(pbs_gc_host* h, const uint64_t* sizes, const in
                                  int64_t oldest_writer, uint8_t* actions, pbs_gc_status* status, double* sweep_ms) {
     const Clock::time_point t0 = Clock::now();
     if (sweep_ms) *sweep_ms = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     const size_t m = h->flags.size();
     int64_t min_atime = 0;
     if ((m && (!sizes || !atimes)) || !sweep_min_atime(phase1_start, oldest_writer, &min_atime)) return PBS_ERR_INVALID;
@@ -223,11 +205,5 @@ extern "C" int pbs_gc_sweep_host(pbs_gc_host* h, const uint64_t* sizes, const in
 }
 
 extern "C" void pbs_gc_end_host(pbs_gc_host* h) {
-    if (!h) return;
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        if (!l.handles.erase(h)) return;
-    }
-    delete h;
+    if (h && Handles::remove(h)) delete h;
 }

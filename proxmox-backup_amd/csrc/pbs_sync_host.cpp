@@ -10,14 +10,13 @@
 #include <chrono>
 #include <cstring>
 #include <exception>
-#include <mutex>
 #include <new>
-#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "gc_common.h"
+#include "live_handles.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_sync.h"
@@ -42,20 +41,7 @@ inline double ms_since(Clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
 }
 
-struct Live {
-    std::mutex mu;
-    std::set<pbs_sync_host*> handles;
-};
-Live& live() {
-    static Live* l = new Live;
-    return *l;
-}
-bool alive(pbs_sync_host* h) {
-    if (!h) return false;
-    Live& l = live();
-    std::lock_guard<std::mutex> g(l.mu);
-    return l.handles.count(h) != 0;
-}
+using Handles = pbs::Live<pbs_sync_host>;
 
 inline std::string key(const uint8_t* d) { return std::string(reinterpret_cast<const char*>(d), 32); }
 
@@ -124,24 +110,20 @@ extern "C" int pbs_sync_begin_host(const uint8_t* store_digests, size_t m, size_
         delete h;
         return PBS_ERR_NOMEM;
     }
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
+    Handles::add(h);
     *out = h;
     if (build_ms) *build_ms = ms_since(t0);
     return PBS_OK;
 }
 
-extern "C" size_t pbs_sync_count_host(pbs_sync_host* h) { return alive(h) ? h->count() : 0; }
+extern "C" size_t pbs_sync_count_host(pbs_sync_host* h) { return Handles::alive(h) ? h->count() : 0; }
 
-extern "C" uint32_t pbs_sync_table_log2_host(pbs_sync_host* h) { return alive(h) ? h->log2 : 0; }
+extern "C" uint32_t pbs_sync_table_log2_host(pbs_sync_host* h) { return Handles::alive(h) ? h->log2 : 0; }
 
 extern "C" int pbs_sync_listing_host(pbs_sync_host* h, uint8_t* digests_out, uint8_t* present_out, size_t cap,
                                      size_t* count) {
     if (count) *count = 0;
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     const size_t k = cap < h->count() ? cap : h->count();
     if (k && digests_out) std::memcpy(digests_out, h->digests.data(), 32 * k);
     if (k && present_out) std::memcpy(present_out, h->present.data(), k);
@@ -150,19 +132,13 @@ extern "C" int pbs_sync_listing_host(pbs_sync_host* h, uint8_t* digests_out, uin
 }
 
 extern "C" int pbs_sync_new_group_host(pbs_sync_host* h) {
-    if (!alive(h) || h->run.open) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || h->run.open) return PBS_ERR_INVALID;
     h->claimed.assign(h->count(), 0);
     return PBS_OK;
 }
 
 extern "C" void pbs_sync_end_host(pbs_sync_host* h) {
-    if (!h) return;
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        if (!l.handles.erase(h)) return;
-    }
-    delete h;
+    if (h && Handles::remove(h)) delete h;
 }
 
 extern "C" int pbs_sync_plan_host(pbs_sync_host* h, const uint8_t* digests, const uint64_t* sizes, size_t n,
@@ -172,7 +148,7 @@ extern "C" int pbs_sync_plan_host(pbs_sync_host* h, const uint8_t* digests, cons
     if (n_fetch) *n_fetch = 0;
     if (n_touch) *n_touch = 0;
     if (plan_ms) *plan_ms = 0;
-    if (!alive(h) || h->run.open ||
+    if (!Handles::alive(h) || h->run.open ||
         !plan_args_valid(h->count(), digests, sizes, n, fetch_store, fetch_entry, fcap, n_fetch, touch_store, tcap, n_touch))
         return PBS_ERR_INVALID;
     const int rc = plan(h, digests, sizes, n, verdict);
@@ -186,7 +162,7 @@ extern "C" int pbs_sync_lists_host(pbs_sync_host* h, uint32_t* fetch_store, uint
                                    size_t* n_fetch, uint32_t* touch_store, size_t tcap, size_t* n_touch) {
     if (n_fetch) *n_fetch = 0;
     if (n_touch) *n_touch = 0;
-    if (!alive(h) || !h->run.open || !n_fetch || !n_touch || (fcap && (!fetch_store || !fetch_entry)) ||
+    if (!Handles::alive(h) || !h->run.open || !n_fetch || !n_touch || (fcap && (!fetch_store || !fetch_entry)) ||
         (tcap && !touch_store))
         return PBS_ERR_INVALID;
     copy_lists(h->run, fetch_store, fetch_entry, fcap, n_fetch, touch_store, tcap, n_touch);
@@ -198,7 +174,7 @@ extern "C" int pbs_sync_submit_host(pbs_sync_host* h, const uint8_t* blobs, cons
                                     pbs_sync_timing* timing) {
     const Clock::time_point t0 = Clock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
-    if (!alive(h) || !submit_args_valid(h->run, blobs, blob_offsets, k)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !submit_args_valid(h->run, blobs, blob_offsets, k)) return PBS_ERR_INVALID;
     IndexRun& run = h->run;
     pbs_sync_timing tm;
     std::memset(&tm, 0, sizeof(tm));
@@ -230,13 +206,13 @@ extern "C" int pbs_sync_submit_host(pbs_sync_host* h, const uint8_t* blobs, cons
 }
 
 extern "C" int pbs_sync_finish_host(pbs_sync_host* h, pbs_sync_result* res) {
-    if (!alive(h) || !h->run.open || h->run.remaining() != 0) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !h->run.open || h->run.remaining() != 0) return PBS_ERR_INVALID;
     close_run(h->run, res);
     return PBS_OK;
 }
 
 extern "C" int pbs_sync_abort_index_host(pbs_sync_host* h) {
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     h->run.clear();
     return PBS_OK;
 }
@@ -252,7 +228,7 @@ extern "C" int pbs_sync_index_image_host(pbs_sync_host* h, const uint8_t* image,
     if (n_entries) *n_entries = 0;
     if (plan_ms) *plan_ms = 0;
     if (index_check) *index_check = PBS_VERIFY_INDEX_OK;
-    if (!alive(h) || h->run.open || !index_check || (vcap && !verdict) ||
+    if (!Handles::alive(h) || h->run.open || !index_check || (vcap && !verdict) ||
         !lists_args_valid(fetch_store, fetch_entry, fcap, n_fetch, touch_store, tcap, n_touch))
         return PBS_ERR_INVALID;
     IndexLayout lo;

@@ -12,14 +12,13 @@
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "dev_arena.h"
 #include "gc_common.h"
 #include "gc_table_dev.h"
+#include "live_handles.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_chunker_internal.h"
@@ -50,8 +49,7 @@ using namespace pbs::gc;
 
 enum VCtr : int { kSkipVerified, kSkipCorrupt, kFailing, kVCtrs };
 
-// One lane per index entry: walks the cluster from the home slot to the first free slot and keeps
-// the LOWEST store position with the entry's digest (equal digests sit in slots of their own).
+// One lane per index entry: the LOWEST store position with the entry's digest (lowest_entry).
 // Present: first[j] = min(first[j], i), and the occurrence is counted by the chunk's state.
 // Absent: miss[i], and the block's count of them for the ordered compaction.
 __global__ __launch_bounds__(kGcThreads) void verify_probe_kernel(
@@ -64,14 +62,7 @@ __global__ __launch_bounds__(kGcThreads) void verify_probe_kernel(
     bool missing = false, sv = false, sc = false;
     if (i < n) {
         const Dig d = load_digest(dig + 32 * i);
-        uint32_t j = kEmpty;
-        uint64_t s = home_slot(d.w[0], shift);
-        for (;;) {
-            const uint32_t k = table[s];
-            if (k == kEmpty) break;
-            if (k < j && same_digest(store, k, d)) j = k;
-            s = (s + 1) & mask;
-        }
+        const uint32_t j = lowest_entry(table, store, d, shift, mask);
         pos[i] = j;
         if (j == kEmpty) {
             missing = true;
@@ -108,31 +99,8 @@ __global__ __launch_bounds__(kGcThreads) void verify_select_kernel(const uint32_
     if (threadIdx.x == 0) block_sel[blockIdx.x] = c;
 }
 
-// The positions with flag != 0, ascending (the scheme of gc_compact_kernel: block_start is the
-// exclusive sum of the blocks' counts, a lane's rank inside its block comes from the ballots);
-// with `gather`, out2[rank] = gather[position] beside it.
-__global__ __launch_bounds__(kGcThreads) void verify_compact_kernel(const uint8_t* __restrict__ flag, uint64_t n,
-                                                                    const unsigned long long* __restrict__ block_start,
-                                                                    uint32_t* __restrict__ out, uint64_t cap,
-                                                                    const uint32_t* __restrict__ gather,
-                                                                    uint32_t* __restrict__ out2) {
-    __shared__ uint32_t wcnt[kGcWaves];
-    const uint64_t i = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x;
-    const bool f = i < n && flag[i] != 0;
-    const unsigned long long b = __ballot(f);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    if (!f) return;
-    uint64_t rank = block_start[blockIdx.x] + __popcll(b & ((1ull << lane) - 1));
-    for (uint32_t w = 0; w < wave; ++w) rank += wcnt[w];
-    if (rank < cap) {
-        out[rank] = (uint32_t)i;
-        if (gather) out2[rank] = gather[i];
-    }
-}
-
-// (verify_magic_kernel, the magic read of a submit: verify_dev.h)
+// (gc_compact_kernel, the ordered compaction with its optional gather: gc_table_dev.h;
+// verify_magic_kernel, the magic read of a submit: verify_dev.h)
 
 // One lane per submitted blob, scattered by store position (the plan names every position once).
 __global__ __launch_bounds__(kGcThreads) void verify_state_kernel(const uint32_t* __restrict__ store_pos,
@@ -166,20 +134,9 @@ ArenaPool& vpool() {
 enum VSlot : unsigned { kVsDig, kVsMiss, kVsSel, kVsCountN, kVsStartN, kVsCountM, kVsStartM, kVsScanTmp, kVsOutMiss,
                         kVsOutStore, kVsOutEntry, kVsCtr, kVsSpans, kVsEnc, kVsOut, kVsPos, kVsStatus, kVsPack };
 
-struct Live {
-    std::mutex mu;
-    std::set<const pbs_verify*> handles;
-};
-Live& live() {
-    static Live* l = new Live;
-    return *l;
-}
-bool alive(const pbs_verify* h) {
-    if (!h) return false;
-    Live& l = live();
-    std::lock_guard<std::mutex> g(l.mu);
-    return l.handles.count(h) != 0;
-}
+constexpr BlobSlots kBlobSlots = {kVsSpans, kVsEnc, kVsOut, kVsPack};
+
+using Handles = Live<pbs_verify>;
 
 void free_handle(pbs_verify* h) {
     DeviceGuard dg(h->dev);
@@ -257,12 +214,12 @@ int plan_on(pbs_verify* h, const uint8_t* digests, const uint64_t* sizes, size_t
         rc.ok(exclusive_sum_u64(tmp, &tb, reinterpret_cast<const uint64_t*>(count_m), reinterpret_cast<uint64_t*>(start_m),
                                 nbm + 1, st))) {
         if (nbn) {
-            hipLaunchKernelGGL(verify_compact_kernel, dim3(nbn), dim3(kGcThreads), 0, st, miss, (uint64_t)n, start_n,
+            hipLaunchKernelGGL(gc_compact_kernel<false>, dim3(nbn), dim3(kGcThreads), 0, st, miss, (uint64_t)n, start_n,
                                out_miss, (uint64_t)n, (const uint32_t*)nullptr, (uint32_t*)nullptr);
             rc.ok(hipGetLastError());
         }
         if (rc.rc == PBS_OK && nbm) {
-            hipLaunchKernelGGL(verify_compact_kernel, dim3(nbm), dim3(kGcThreads), 0, st, sel, (uint64_t)m, start_m,
+            hipLaunchKernelGGL(gc_compact_kernel<true>, dim3(nbm), dim3(kGcThreads), 0, st, sel, (uint64_t)m, start_m,
                                out_store, (uint64_t)kcap, (const uint32_t*)h->d_first, out_entry);
             rc.ok(hipGetLastError());
         }
@@ -306,34 +263,6 @@ int plan_on(pbs_verify* h, const uint8_t* digests, const uint64_t* sizes, size_t
     return PBS_OK;
 }
 
-// enc[t] for k blobs given as (start, length) pairs in `blobs_dev`; synchronous
-int read_magics(pbs_verify* h, DevArena& ar, const uint8_t* blobs_dev, const std::vector<uint64_t>& spans, size_t k,
-                std::vector<uint8_t>& enc, double* ms_out) {
-    enc.assign(k, 0);
-    if (k == 0) return PBS_OK;
-    hipStream_t st = h->st;
-    uint64_t* d_spans = ar.get<uint64_t>(kVsSpans, 16 * k);
-    uint8_t* d_enc = ar.get<uint8_t>(kVsEnc, k);
-    hipEvent_t e0 = ar.event(2), e1 = ar.event(3);
-    if (!d_spans || !d_enc) return PBS_ERR_NOMEM;
-    if (!e0 || !e1) return PBS_ERR_HIP;
-    CallRc rc;
-    (void)hipGetLastError();
-    if (rc.ok(hipMemcpyAsync(d_spans, spans.data(), 16 * k, hipMemcpyHostToDevice, st)) && rc.ok(hipEventRecord(e0, st))) {
-        hipLaunchKernelGGL(verify_magic_kernel, dim3(blocks_for(k)), dim3(kGcThreads), 0, st, blobs_dev, d_spans,
-                           (uint64_t)k, d_enc);
-        rc.ok(hipGetLastError()) && rc.ok(hipEventRecord(e1, st)) &&
-            rc.ok(hipMemcpyAsync(enc.data(), d_enc, k, hipMemcpyDeviceToHost, st));
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) rc.fail(PBS_ERR_HIP);
-    if (rc.rc == PBS_OK && ms_out) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *ms_out = ms;
-    }
-    return rc.rc;
-}
-
 // pbs_verify_submit after the argument checks; the caller has set the device.  Nothing of the
 // run changes unless every step went well.
 int submit_on(pbs_verify* h, const uint8_t* blobs_dev, const uint64_t* blob_offsets, const uint8_t* load_failed,
@@ -350,59 +279,17 @@ int submit_on(pbs_verify* h, const uint8_t* blobs_dev, const uint64_t* blob_offs
     }
     const size_t item0 = run.done;
     ArenaLease ar(vpool(), h->dev);
-    if (!blobs_dev) {  // (k empty files: the decoder still wants an address)
-        blobs_dev = ar->get<uint8_t>(kVsPack, 1);
-        if (!blobs_dev) return PBS_ERR_NOMEM;
-    }
-    std::vector<uint64_t> spans(2 * k);
-    for (size_t t = 0; t < k; ++t) {
-        spans[2 * t] = blob_offsets[t];
-        spans[2 * t + 1] = load_failed && load_failed[t] ? 0 : blob_offsets[t + 1] - blob_offsets[t];
-    }
-    std::vector<uint8_t> enc;
-    int rc = read_magics(h, *ar, blobs_dev, spans, k, enc, &tm.magic_ms);
-    if (rc != PBS_OK) return rc;
-
-    // the decoder takes blobs that follow one another: a run of items between two load failures per call
     std::vector<uint8_t> kinds(k, PBS_BLOB_KIND_NONE), status(k, PBS_VERIFY_ST_LOAD_FAILED);
-    std::vector<uint64_t> csz, ooff, olens;
-    for (size_t a = 0; a < k;) {
-        if (load_failed && load_failed[a]) {
-            ++a;
-            continue;
-        }
-        size_t b = a;
-        while (b < k && !(load_failed && load_failed[b])) ++b;
-        const size_t cnt = b - a;
-        csz.assign(cnt, 0);
-        uint64_t total = 0;
-        bool plain = false;
-        for (size_t t = a; t < b; ++t) {
-            tm.encrypted += enc[t];
-            if (enc[t]) continue;  // verified by its CRC alone: a zero-length slot
-            plain = true;
-            csz[t - a] = run.todo_sizes[item0 + t];
-            if (csz[t - a] > UINT64_MAX - total) return PBS_ERR_NOMEM;
-            total += csz[t - a];
-        }
-        if (total > SIZE_MAX) return PBS_ERR_NOMEM;
-        // (an all-encrypted run takes no output scratch at all)
-        uint8_t* d_out = plain ? ar->get<uint8_t>(kVsOut, (size_t)total, false) : nullptr;
-        if (plain && !d_out) return PBS_ERR_NOMEM;
-        ooff.assign(cnt + 1, 0);
-        olens.assign(cnt, 0);
-        pbs_blob_decode_inflate_timing dt;
-        rc = pbs_blob_decode_inflate_device(blobs_dev, blob_offsets + a, cnt, nullptr, &run.todo_digests[32 * (item0 + a)],
-                                            csz.data(), 1, d_out, (size_t)total, ooff.data(), olens.data(),
-                                            kinds.data() + a, status.data() + a, &dt, st);
-        if (rc != PBS_OK) return rc;
-        tm.decode_ms += dt.base.total_ms;
-        tm.decoded += cnt;
-        tm.scratch_bytes += total;
-        a = b;
-    }
-    for (size_t t = 0; t < k; ++t)
-        if (status[t] == PBS_BLOB_ST_NO_CONFIG) status[t] = PBS_BLOB_ST_OK;  // load_chunk + verify_unencrypted: Ok
+    BlobTiming bt;
+    const int rc = blob_verdicts(*ar, kBlobSlots, st, blobs_dev, blob_offsets, load_failed, &run.todo_digests[32 * item0],
+                                 [&](size_t t) { return run.todo_sizes[item0 + t]; }, k, kinds.data(), status.data(),
+                                 nullptr, &bt);
+    if (rc != PBS_OK) return rc;
+    tm.magic_ms = bt.magic_ms;
+    tm.decode_ms = bt.decode_ms;
+    tm.decoded = bt.decoded;
+    tm.encrypted = bt.encrypted;
+    tm.scratch_bytes = bt.scratch_bytes;
 
     // the states
     uint32_t* d_sp = ar->get<uint32_t>(kVsPos, 4 * k);
@@ -515,17 +402,13 @@ extern "C" int pbs_verify_begin(const uint8_t* store_digests, size_t m, pbs_veri
         free_handle(h);
         return rc.rc;
     }
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
+    Handles::add(h);
     *out = h;
     return PBS_OK;
 }
 
 extern "C" int pbs_verify_states(pbs_verify* h, uint8_t* states_host, size_t m) {
-    if (!alive(h) || m != h->m || (m && !states_host)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || m != h->m || (m && !states_host)) return PBS_ERR_INVALID;
     if (m == 0) return PBS_OK;
     DeviceGuard dg(h->dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
@@ -536,13 +419,7 @@ extern "C" int pbs_verify_states(pbs_verify* h, uint8_t* states_host, size_t m) 
 }
 
 extern "C" void pbs_verify_end(pbs_verify* h) {
-    if (!h) return;
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        if (!l.handles.erase(h)) return;
-    }
-    free_handle(h);
+    if (h && Handles::remove(h)) free_handle(h);
 }
 
 extern "C" int pbs_verify_plan(pbs_verify* h, const uint8_t* digests, const uint64_t* sizes, size_t n, int index_mode,
@@ -550,7 +427,7 @@ extern "C" int pbs_verify_plan(pbs_verify* h, const uint8_t* digests, const uint
                                double* plan_ms) {
     if (n_todo) *n_todo = 0;
     if (plan_ms) *plan_ms = 0;
-    if (!alive(h) || h->run.open ||
+    if (!Handles::alive(h) || h->run.open ||
         !plan_args_valid(digests, sizes, n, index_mode, todo_store, todo_entry, cap, n_todo))
         return PBS_ERR_INVALID;
     DeviceGuard dg(h->dev);
@@ -573,7 +450,7 @@ extern "C" int pbs_verify_plan(pbs_verify* h, const uint8_t* digests, const uint
 }
 
 extern "C" int pbs_verify_abort_index(pbs_verify* h) {
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     h->run.clear();
     return PBS_OK;
 }
@@ -582,7 +459,7 @@ extern "C" int pbs_verify_submit(pbs_verify* h, const uint8_t* blobs_dev, const 
                                  const uint8_t* load_failed, size_t k, uint8_t* kinds, uint8_t* status,
                                  pbs_verify_timing* timing) {
     if (timing) std::memset(timing, 0, sizeof(*timing));
-    if (!alive(h) || !submit_args_valid(h->run, blobs_dev, blob_offsets, k)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !submit_args_valid(h->run, blobs_dev, blob_offsets, k)) return PBS_ERR_INVALID;
     DeviceGuard dg(h->dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
     try {
@@ -596,7 +473,7 @@ extern "C" int pbs_verify_finish(pbs_verify* h, pbs_verify_result* res, uint32_t
                                  size_t* n_corrupt, uint32_t* missing_pos, size_t mcap, size_t* n_missing) {
     if (n_corrupt) *n_corrupt = 0;
     if (n_missing) *n_missing = 0;
-    if (!alive(h) || !finish_args_valid(h->run, corrupt_store, ccap, missing_pos, mcap)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !finish_args_valid(h->run, corrupt_store, ccap, missing_pos, mcap)) return PBS_ERR_INVALID;
     DeviceGuard dg(h->dev);
     if (!dg.ok) return PBS_ERR_NO_DEVICE;
     return finish_on(h, res, corrupt_store, ccap, n_corrupt, missing_pos, mcap, n_missing);
@@ -610,7 +487,7 @@ extern "C" int pbs_verify_index_device(pbs_verify* h, const uint8_t* image, size
     if (res) std::memset(res, 0, sizeof(*res));
     if (n_corrupt) *n_corrupt = 0;
     if (n_missing) *n_missing = 0;
-    if (!alive(h) || h->run.open || !mode_valid(index_mode) || (ccap && !corrupt_store) || (mcap && !missing_pos))
+    if (!Handles::alive(h) || h->run.open || !mode_valid(index_mode) || (ccap && !corrupt_store) || (mcap && !missing_pos))
         return PBS_ERR_INVALID;
     const size_t m = h->m;
     if (m && !store_offsets) return PBS_ERR_INVALID;
@@ -645,7 +522,7 @@ extern "C" int pbs_verify_index_device(pbs_verify* h, const uint8_t* image, size
             spans[2 * t] = store_offsets[run.todo_store[t]];
             spans[2 * t + 1] = blob_len(t);
         }
-        rc = read_magics(h, *ar, store_blobs_dev, spans, k, enc, nullptr);
+        rc = magic_flags(*ar, kBlobSlots, h->st, store_blobs_dev, spans, k, enc, nullptr);
         std::vector<uint64_t> src, dst, lens, offs;
         for (size_t t0 = 0; rc == PBS_OK && t0 < k;) {
             const size_t t1 = batch_end(run, t0, budget_bytes, enc.data(), blob_len);

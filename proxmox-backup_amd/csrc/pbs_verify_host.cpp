@@ -12,12 +12,11 @@
 #include <chrono>
 #include <cstring>
 #include <exception>
-#include <mutex>
 #include <new>
-#include <set>
 #include <vector>
 
 #include "gc_common.h"
+#include "live_handles.h"
 #include "pbs_blob.h"
 #include "pbs_chunker.h"
 #include "pbs_digest.h"
@@ -53,20 +52,7 @@ inline uint64_t be64(const uint8_t* p) {
     return v;
 }
 
-struct Live {
-    std::mutex mu;
-    std::set<pbs_verify_host*> handles;
-};
-Live& live() {
-    static Live* l = new Live;
-    return *l;
-}
-bool alive(pbs_verify_host* h) {
-    if (!h) return false;
-    Live& l = live();
-    std::lock_guard<std::mutex> g(l.mu);
-    return l.handles.count(h) != 0;
-}
+using Handles = pbs::Live<pbs_verify_host>;
 
 // the lowest store position carrying the digest `d`
 inline uint32_t lowest(const pbs_verify_host& h, const uint8_t* d) {
@@ -157,7 +143,7 @@ int submit(pbs_verify_host* h, const uint8_t* blobs, const uint64_t* blob_offset
            size_t k, uint8_t* kinds, uint8_t* status, pbs_verify_timing* timing) {
     const Clock::time_point t0 = Clock::now();
     if (timing) std::memset(timing, 0, sizeof(*timing));
-    if (!alive(h) || !submit_args_valid(h->run, blobs, blob_offsets, k)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !submit_args_valid(h->run, blobs, blob_offsets, k)) return PBS_ERR_INVALID;
     IndexRun& run = h->run;
     pbs_verify_timing tm;
     std::memset(&tm, 0, sizeof(tm));
@@ -192,7 +178,7 @@ int finish(pbs_verify_host* h, pbs_verify_result* res, uint32_t* corrupt_store, 
            uint32_t* missing_pos, size_t mcap, size_t* n_missing) {
     if (n_corrupt) *n_corrupt = 0;
     if (n_missing) *n_missing = 0;
-    if (!alive(h) || !finish_args_valid(h->run, corrupt_store, ccap, missing_pos, mcap)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || !finish_args_valid(h->run, corrupt_store, ccap, missing_pos, mcap)) return PBS_ERR_INVALID;
     uint64_t failing = 0;
     for (size_t i = 0; i < h->run.n; ++i) {
         const uint32_t j = h->pos[i];
@@ -207,7 +193,7 @@ int plan(pbs_verify_host* h, const uint8_t* digests, const uint64_t* sizes, size
     const Clock::time_point t0 = Clock::now();
     if (n_todo) *n_todo = 0;
     if (plan_ms) *plan_ms = 0;
-    if (!alive(h) || h->run.open ||
+    if (!Handles::alive(h) || h->run.open ||
         !plan_args_valid(digests, sizes, n, index_mode, todo_store, todo_entry, cap, n_todo))
         return PBS_ERR_INVALID;
     IndexRun& run = h->run;
@@ -289,30 +275,20 @@ extern "C" int pbs_verify_begin_host(const uint8_t* store_digests, size_t m, pbs
         delete h;
         return PBS_ERR_NOMEM;
     }
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        l.handles.insert(h);
-    }
+    Handles::add(h);
     *out = h;
     if (build_ms) *build_ms = ms_since(t0);
     return PBS_OK;
 }
 
 extern "C" int pbs_verify_states_host(pbs_verify_host* h, uint8_t* states_host, size_t m) {
-    if (!alive(h) || m != h->state.size() || (m && !states_host)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h) || m != h->state.size() || (m && !states_host)) return PBS_ERR_INVALID;
     if (m) std::memcpy(states_host, h->state.data(), m);
     return PBS_OK;
 }
 
 extern "C" void pbs_verify_end_host(pbs_verify_host* h) {
-    if (!h) return;
-    {
-        Live& l = live();
-        std::lock_guard<std::mutex> g(l.mu);
-        if (!l.handles.erase(h)) return;
-    }
-    delete h;
+    if (h && Handles::remove(h)) delete h;
 }
 
 extern "C" int pbs_verify_plan_host(pbs_verify_host* h, const uint8_t* digests, const uint64_t* sizes, size_t n,
@@ -322,7 +298,7 @@ extern "C" int pbs_verify_plan_host(pbs_verify_host* h, const uint8_t* digests, 
 }
 
 extern "C" int pbs_verify_abort_index_host(pbs_verify_host* h) {
-    if (!alive(h)) return PBS_ERR_INVALID;
+    if (!Handles::alive(h)) return PBS_ERR_INVALID;
     h->run.clear();
     return PBS_OK;
 }
@@ -346,7 +322,7 @@ extern "C" int pbs_verify_index_host(pbs_verify_host* h, const uint8_t* image, s
     if (res) std::memset(res, 0, sizeof(*res));
     if (n_corrupt) *n_corrupt = 0;
     if (n_missing) *n_missing = 0;
-    if (!alive(h) || h->run.open || !mode_valid(index_mode) || (ccap && !corrupt_store) || (mcap && !missing_pos))
+    if (!Handles::alive(h) || h->run.open || !mode_valid(index_mode) || (ccap && !corrupt_store) || (mcap && !missing_pos))
         return PBS_ERR_INVALID;
     const size_t m = h->state.size();
     if (m && !store_offsets) return PBS_ERR_INVALID;
